@@ -13,6 +13,12 @@ scaling); the only collectives are the timing barrier, a MAX over ranks of the e
 the per-rank figures. `--gpus N` without a torchrun environment launches the N ranks from here, BEFORE this
 process touches the GPU, and fails if fewer than N devices are visible. Under torchrun, `--gpus` must equal
 WORLD_SIZE.
+
+A plain run sets up, warms up, times the steps and prints the JSON line; the figures derived from the timed steps
+themselves (solve statistics, modelled roofline, issue model) come with it. `--full` adds everything that takes runs
+of its own: the secondary passes, the live PMC traffic passes, the host-boundary variant and the CPU baseline.
+`--dump-outputs DIR` writes what the last timed step computed (x, u, K, k and the per-instance statistics) as
+DIR/<name>.npy, float64.
 """
 import argparse
 import json
@@ -65,29 +71,34 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=1024, help="instances per GPU")
     ap.add_argument("--config", default="acrobot")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: secondary passes, PMC traffic, host boundary, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (x, u, K, k, solve statistics) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the two rocprofv3 --pmc child passes that measure HBM traffic of the solve kernel live")
+                    help="with --full: skip the two rocprofv3 --pmc child passes that measure HBM traffic of the solve kernel live")
     ap.add_argument("--distinct-shards", action="store_true",
                     help="rank r solves instances [r*B, (r+1)*B) of one big synthetic batch (BASELINE config 4's meaning of sharding; "
                          "the DEFAULT for --gpus N > 1; at N = 1 the shard is [0, B) either way)")
     ap.add_argument("--same-instances", action="store_true",
                     help="every rank solves the SAME B instances [0, B) (fixed per-GPU work: weak scaling is then perfect by construction; "
-                         "reported as secondary.same_instances in the default run)")
+                         "reported as secondary.same_instances by --full)")
     ap.add_argument("--inflight", type=int, default=1,
                     help="solver handles used round-robin on separate HIP streams (1 = strictly sequential steps, "
                          "the headline setting; 2 lets the next batch fill SIMDs freed by early finishers)")
     ap.add_argument("--generator", default="splitmix64", choices=["pcg64", "splitmix64"],
                     help="synthetic inputs: the library's own ilqr_synthetic_inputs (SURVEY 8(d) / BASELINE.md: splitmix64 / Box-Muller, "
                          "seed 20240607 — what the cpu_baseline leg, a C host and bench/julia_ref.jl regenerate; the default since round 6) "
-                         "or numpy PCG64 streams (the inputs of the figures of rounds 1-5; reported as secondary.pcg64 by the default run)")
+                         "or numpy PCG64 streams (the inputs of the figures of rounds 1-5; reported as secondary.pcg64 by --full)")
     ap.add_argument("--variant", default="auto", choices=["auto", "latency", "throughput", "packed", "mid", "packed1", "packed2"])
     ap.add_argument("--shared-step", action="store_true",
                     help="optional mode, NOT the reference's behaviour and not the headline: one Armijo step size per inner iteration "
                          "for the whole (multi-GPU) batch, decided on the summed merit — one all-reduce (RCCL over xGMI) of three "
                          "doubles per line-search trial, line search stepped from the host (Solver.solve_shared_step_)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the two short secondary passes (distinct shards per rank; two batches in flight) reported as extra keys")
+                    help="with --full: skip the short secondary passes (distinct shards per rank; two batches in flight; PCG64 inputs; "
+                         "the slowest instance alone) reported as extra keys")
     ap.add_argument("--sharded-handle", action="store_true",
                     help="ONE process, ONE solver handle over the first N devices (ilqr_create_sharded: what a Julia host holding one "
                          "Solver would use) instead of one process per GPU; same JSON line, ranks.launcher says so")
@@ -174,8 +185,8 @@ class _StubSolver:
     """Stands in for the GPU solver in the CPU test of the multi-rank path (ILQR_BENCH_STUB=1): same call sequence,
     the 'solve' is a sleep that depends on the rank so that MAX-over-ranks is observable."""
 
-    def __init__(self, rank, batch):
-        self.rank, self.B, self.nx, self.nu, self.nc_stage, self.nc_term = rank, batch, 4, 1, 0, 4
+    def __init__(self, rank, batch, horizon=2):
+        self.rank, self.B, self.T, self.nx, self.nu, self.nc_stage, self.nc_term = rank, batch, horizon, 4, 1, 0, 4
 
     def reset_(self): pass
     def initialize_rollout_device_(self, a, b): pass
@@ -185,14 +196,42 @@ class _StubSolver:
     def synchronize(self): pass
     def timing(self): return 2.0 * (self.rank + 1), 1
     def timing_reset(self): pass
-    def get_trajectory(self): return None
-    def get_policy(self): return None
+    def get_trajectory(self): return np.full((self.B, self.T, self.nx), float(self.rank)), np.zeros((self.B, self.T - 1, self.nu))
+    def get_policy(self): return np.zeros((self.B, self.T - 1, self.nx, self.nu)), np.zeros((self.B, self.T - 1, self.nu))
     def close(self): pass
 
     def stats(self):
         it = np.full(self.B, 10 + self.rank)
         return {"iterations": it, "rollouts": it + 1, "outer_iterations": np.full(self.B, 2),
                 "max_violation": np.zeros(self.B)}
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(sol, out_dir, suffix="", limit=DUMP_LIMIT_BYTES):
+    """What a caller of the timed path receives from its last step: x, u (get_trajectory), K, k (get_policy) and the per-instance
+    solve statistics (stats_<field>), as out_dir/<name><suffix>.npy in float64. A batch whose arrays exceed `limit` bytes is cut
+    to a fixed, seeded sample of instances, the same for every run of the same arguments; instances<suffix>.npy then lists them."""
+    x, u = sol.get_trajectory()
+    K, k = sol.get_policy()
+    arrays = {"x": x, "u": u, "K": K, "k": k}
+    for f, v in sol.stats().items():
+        arrays["stats_" + f] = v
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    B = x.shape[0]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        n = max(1, int(limit // (total / B + 8)))          # + 8: the instance index
+        keep = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, n, replace=False))
+        arrays = {name: a[keep] for name, a in arrays.items()}
+        arrays["instances"] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 # ------------------------------------------------------------------------------------------------ one rank
@@ -258,7 +297,7 @@ def worker(args, solver_factory=None):
         else:
             x1, ub = np.tile(x1, (ndev, 1)), np.tile(ub, (ndev, 1, 1))
     if stub:
-        sols = [solver_factory(rank, model, T, B, x1, ub) if solver_factory is not None else _StubSolver(rank, B)]
+        sols = [solver_factory(rank, model, T, B, x1, ub) if solver_factory is not None else _StubSolver(rank, B, T)]
         d_x1 = d_u = None
     else:
         if sharded:
@@ -319,6 +358,9 @@ def worker(args, solver_factory=None):
     my_elapsed = time.perf_counter() - t0
     barrier()
     elapsed = pkg.distributed.max_over_ranks(my_elapsed, dist, cdev)
+    if args.dump_outputs:
+        # the handle of the last timed step, before any --full pass reuses it; rank r > 0 suffixes its files, the ranks share the limit
+        dump_outputs(sols[(counter[0] - 1) % len(sols)], args.dump_outputs, "_rank%d" % rank if rank else "", DUMP_LIMIT_BYTES // world)
 
     kernel_ms, launches = sol.timing()
     st = sol.stats()
@@ -346,7 +388,7 @@ def worker(args, solver_factory=None):
     # [rB, (r+1)B) of one big synthetic batch (BASELINE config 4's situation: the step then lasts as long as the unluckiest
     # shard's slowest instance), and two batches in flight per GPU (the next batch fills SIMDs freed by early finishers)
     secondary = {}
-    if not args.shared_step and not args.no_secondary and solver_factory is None and not sharded:
+    if args.full and not args.shared_step and not args.no_secondary and solver_factory is None and not sharded:
         k2 = max(1, min(3, args.steps))
 
         def timed(step_fn, handles):
@@ -521,7 +563,7 @@ def worker(args, solver_factory=None):
                 # stage-materialised model a resident solve sits
                 "io_lower_bound_bytes_per_launch": io_bytes,
                 "io_lower_bound_GBs": io_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms > 0 else 0.0}
-        if world == 1 and not args.no_pmc and not args.shared_step and not sharded:
+        if args.full and world == 1 and not args.no_pmc and not args.shared_step and not sharded:
             for s_ in sols:
                 s_.synchronize()
             tr, why = measure_traffic(args)
@@ -590,7 +632,7 @@ def worker(args, solver_factory=None):
                                                    "dependences counted (rollout_step_chain, riccati_step_chain): what more issue bandwidth could reach")
         out["roofline"] = roof
 
-        if world == 1:
+        if args.full and world == 1:
             # the same step with the boundary fed HOST buffers: x1, ū over PCIe in, x, u, K, k over PCIe out
             # (reported beside `value`, never as `value`)
             h0 = time.perf_counter()
@@ -605,7 +647,7 @@ def worker(args, solver_factory=None):
             out["host_boundary"] = {"value": ndev * B / host_elapsed, "unit": "trajectories/s",
                                     "note": "one rank, inputs from host memory and x, u, K, k copied back (PCIe-inclusive)"}
 
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle as O
             threads = host_cores()
             sample = min(B, 64 * threads)

@@ -99,3 +99,52 @@ def test_sharded_handle_mode_refuses_without_enough_devices():
     assert p.returncode != 0
     err = p.stderr.decode()
     assert "needs a GPU" in err or "device(s) visible" in err
+
+
+def test_plain_run_leaves_the_extra_passes_to_full():
+    """A plain run times its steps and prints the line; the secondary passes come with --full only (stub solve, 2 ranks over gloo)."""
+    base = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8"]
+    outs = []
+    for extra in ([], ["--full"]):
+        p = _run(base + extra, ILQR_BENCH_STUB="1")
+        assert p.returncode == 0, p.stderr.decode()[-2000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        outs.append(json.loads(lines[0]))
+    plain, full = outs
+    for out in outs:
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+        assert out["unit"] == "trajectories/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert "secondary" not in plain
+    assert "same_instances" in full["secondary"]
+
+
+def test_dump_outputs_writes_the_last_step_as_float_npy(tmp_path):
+    """--dump-outputs DIR: x, u, K, k and the per-instance statistics of the last timed step, float64, shapes of the batch (stub)."""
+    import numpy as np
+    p = _run(["--gpus", "1", "--steps", "2", "--warmup", "0", "--batch", "8", "--config", "acrobot51", "--dump-outputs", str(tmp_path)],
+             ILQR_BENCH_STUB="1")
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    names = sorted(f[:-4] for f in os.listdir(tmp_path))
+    assert {"x", "u", "K", "k", "stats_iterations", "stats_rollouts"} <= set(names) and "instances" not in names
+    a = {n: np.load(tmp_path / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["x"].shape == (8, 51, 4) and a["u"].shape == (8, 50, 1) and a["K"].shape == (8, 50, 4, 1) and a["k"].shape == (8, 50, 1)
+    assert (a["stats_iterations"] == 10).all()
+
+
+def test_dump_outputs_samples_a_batch_beyond_the_limit(tmp_path):
+    """Beyond the size limit the dump is a fixed, seeded sample of instances, the same on every call, listed in instances.npy."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    sol = bench._StubSolver(0, 1000, 11)
+    limit = 64 << 10
+    for d in ("a", "b"):
+        bench.dump_outputs(sol, str(tmp_path / d), limit=limit)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= limit + 128 * len(os.listdir(tmp_path / "a"))          # + the .npy headers
+    idx = np.load(tmp_path / "a" / "instances.npy")
+    assert 0 < len(idx) < 1000 and (np.diff(idx) > 0).all()
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "instances.npy"))
+    assert np.load(tmp_path / "a" / "x.npy").shape == (len(idx), 11, 4)
