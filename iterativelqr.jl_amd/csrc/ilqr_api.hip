@@ -137,6 +137,8 @@ struct ilqr_handle {
 
 namespace {
 
+bool has_kernel(const ilqr_model_vtable* vt, int k) { return (vt->kernels >> k & 1u) != 0; }
+
 ilqr::KArgs make_args(const ilqr_handle* h) {
     ilqr::KArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.constrained = h->constrained; a.stage = 0; a.opt = h->opt;
@@ -968,7 +970,7 @@ int ilqr_create(const ilqr_problem_desc* d, ilqr_handle** out) {
     ilqr_default_options(&h->opt);
     fill_buffers(h);
     h->lds_fits = h->lds_bytes <= 160 * 1024;
-    if (!h->lds_fits && vt->launch_solve_packed == nullptr) {
+    if (!h->lds_fits && !has_kernel(vt, ilqr::K_PACKED1)) {
         // the reference has no horizon limit (src/data/problem.jl:25-46); here only the streaming (packed) kernel is free of one
         delete h;
         return fail(ILQR_ERR_LDS, "per-instance working set exceeds the 160 KiB LDS of a gfx950 CU and this model has no "
@@ -989,8 +991,8 @@ int ilqr_create(const ilqr_problem_desc* d, ilqr_handle** out) {
     }
     h->ws_bytes = (size_t)h->B * (size_t)h->L.stride * 8;
     if ((e = hipMalloc((void**)&h->ws, h->ws_bytes)) != hipSuccess) return bail(e, "hipMalloc(workspace)");
-    if (vt->launch_solve_packed != nullptr && (e = hipMalloc((void**)&h->done_counter, sizeof(int))) != hipSuccess) return bail(e, "hipMalloc(hand-over counter)");
-    if (vt->launch_solve_packed != nullptr && (e = hipMalloc((void**)&h->pool, sizeof(int) * (size_t)(ilqr::POOL_Q + h->B + ilqr::POOL_CUS))) != hipSuccess) return bail(e, "hipMalloc(hand-over queue)");
+    if (has_kernel(vt, ilqr::K_PACKED1) && (e = hipMalloc((void**)&h->done_counter, sizeof(int))) != hipSuccess) return bail(e, "hipMalloc(hand-over counter)");
+    if (has_kernel(vt, ilqr::K_PACKED1) && (e = hipMalloc((void**)&h->pool, sizeof(int) * (size_t)(ilqr::POOL_Q + h->B + ilqr::POOL_CUS))) != hipSuccess) return bail(e, "hipMalloc(hand-over queue)");
     if ((e = hipMemsetAsync(h->ws, 0, h->ws_bytes, h->stream)) != hipSuccess) return bail(e, "hipMemsetAsync");
     if (!ilqr::is_large_model(vt->nx, vt->nu) && (e = hipMalloc((void**)&h->cu_slots, sizeof(int) * ilqr::CU_SLOT_INTS * ilqr::CU_SLOT_CUS)) != hipSuccess) return bail(e, "hipMalloc(role table)");
     if (h->pool && (e = hipMemsetAsync(h->pool, 0, sizeof(int) * (size_t)(ilqr::POOL_Q + h->B + ilqr::POOL_CUS), h->stream)) != hipSuccess) return bail(e, "hipMemsetAsync(hand-over queue)");
@@ -1178,15 +1180,18 @@ int ilqr_initialize_rollout(ilqr_handle* h, const double* x1, const double* u) {
     return ILQR_OK;
 }
 
-// Large models whose matrices are single tiles (nx, nu <= 16): the four-wave kernel holds 2 instances per CU, the one-wave kernel SIX
-// (248 VGPRs and 25 KB of LDS per wave: profiles/r04_synth12_b4096_mid_rocprofv3.txt).
-// An instance alone is faster on four waves (its windows run their tiles side by side: 3.9 k against 5.3 k clk per Riccati step on
-// synth12, the rollout beside the sensitivity sweep instead of behind it), so auto takes one wave per instance only where residency
-// wins: beyond 8 instances per CU the four-wave kernel works in more than four rounds (tools/mid_bench.py: equal at 2048 instances
-// on 256 CUs, 1.28x at 4096, 1.47x at 8192).
-static bool use_mid(const ilqr_handle* h) {
-    if (h->vt->launch_solve_mid == nullptr) return false;
-    return h->variant == 4 || (h->variant == 0 && h->B > 2 * h->num_simds);
+// what the launch plan (ilqr_launch_plan.hpp) reads of the handle
+static ilqr::LaunchIn launch_in(const ilqr_handle* h) {
+    static const bool role_slots = !(std::getenv("ILQR_ROLE_SLOTS") && std::getenv("ILQR_ROLE_SLOTS")[0] == '0');
+    ilqr::LaunchIn in;
+    in.variant = h->variant; in.B = h->B; in.num_simds = h->num_simds;
+    in.lds_fits = h->lds_fits; in.lds_bytes = h->lds_bytes; in.slim_lds_bytes = (size_t)h->L.lds_doubles_slim * 8;
+    in.kernels = h->vt->kernels; in.packed1_lds_bytes = h->vt->packed1_lds_bytes; in.packed2_lds_bytes = h->vt->packed2_lds_bytes;
+    in.constrained = h->constrained != 0; in.max_dual_updates = h->opt.max_dual_updates;
+    in.handover = h->handover; in.handover_live = h->handover_live; in.handover_mark = h->handover_mark;
+    in.done_counter = h->done_counter != nullptr; in.pool = h->pool != nullptr; in.cu_slots = h->cu_slots != nullptr;
+    in.role_slots = role_slots;
+    return in;
 }
 
 int ilqr_initialize_rollout_resident(ilqr_handle* h) {
@@ -1210,87 +1215,32 @@ int ilqr_solve(ilqr_handle* h) {
     auto drop = [&](int rc) { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); return rc; };
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, h->stream) != hipSuccess)
         return drop(fail(ILQR_ERR_HIP, "hipEventCreate/Record failed"));
-    // auto: the latency kernel while the batch fits the chip (one instance per SIMD); larger batches take the packed
-    // kernel (four instances per wave, workspace streamed from HBM / L2) when the model has one (nx, nu <= 4),
-    // the throughput kernel otherwise.
-    // Horizons whose LDS-resident set exceeds 160 KiB run on the packed kernel only.
-    const bool can_pack = h->vt->launch_solve_packed != nullptr;
-    const bool packed = can_pack && (h->variant == 3 || h->variant == 5 || h->variant == 6 || !h->lds_fits || (h->variant == 0 && h->B > h->num_simds));
-    const bool slim = !packed && h->vt->launch_solve_slim != nullptr &&
-                      (h->variant == 2 || (h->variant == 0 && h->B > h->num_simds));
-    if (!packed && !h->lds_fits) return drop(fail(ILQR_ERR_LDS, "this horizon only runs on the packed kernel"));
-    if (packed) {
-        // straggler hand-over: the survivors of a batch leave the packed kernel and are finished by the latency kernel (two waves
-        // per instance, LDS-resident state; a rejected line-search trial costs it one rollout where it costs the packed kernel a
-        // whole cycle of the wave) in a launch that follows on the stream. By head count (the default) — once no more than `live`
-        // instances of the batch are still running, each of them leaves at the next head of an inner or outer iteration;
-        // auto: live = min(1024, B / 4), what the latency kernel holds at full speed. By outer iteration (ilqr_set_handover(k >= 2))
-        // — an instance entering outer iteration k leaves at that boundary. Both kernels do the same arithmetic, so which
-        // instances change kernels, and when, never shows in a result.
-        // (Measured and dropped: a pool of latency workgroups BESIDE the packed kernel taking leavers from a device queue — at
-        // 8192 instances the packed kernel's 2048 waves fill every CU, a pool workgroup only starts once they retire)
-        int ho = h->handover < 0 ? 0 : h->handover;
-        int live = h->handover < 0 ? (h->handover_live < 0 ? std::min(1024, h->B / 4) : h->handover_live) : 0;
-        const bool can = h->constrained && h->lds_fits && h->done_counter != nullptr;
-        if (!can || ho < 2 || ho > h->opt.max_dual_updates) ho = 0;
-        if (!can) live = 0;
-        a.handover_outer = ho; a.handover_live = live;
-        if (live > 0) HIP_TRY(hipMemsetAsync(h->done_counter, 0, sizeof(int), h->stream));
-        // the one-wave form's workgroups finish the instances handed over themselves (ilqr_device_packed.hpp: solve_kernel_packed);
-        // under the head-count rule an instance whose rejected line-search trials exceed the batch's mean by `mark` leaves at once
-        if ((ho > 0 || live > 0) && h->pool != nullptr) {
-            HIP_TRY(hipMemsetAsync(h->pool, 0, sizeof(int) * (size_t)(ilqr::POOL_Q + h->B + ilqr::POOL_CUS), h->stream));
-            // a marked straggler gets its CU to itself (config 4, shard 6: 126.6 -> 118.0 ms) — while the launch is ONE round of
-            // workgroups (four of them per CU): in a launch of several rounds a workgroup that waits holds the slots the next round
-            // needs, so there nobody waits (pool_cu = 0: no CU is vacated, an idle worker leaves as soon as the queue is empty)
-            a.pool_cu = ((h->B + 3) / 4 + 1) / 2 <= h->num_simds ? 1 : 0;
-            a.pool = h->pool; a.pool_lds = (int)h->lds_bytes;
-            h->pool_valid = true;
-            a.pool_mark = live > 0 ? (h->handover_mark < 0 ? 6 : h->handover_mark) : 0;
-            if (!a.pool_cu) a.pool_mark = 0;      // (and nobody is marked: the batch's mean says nothing while half the batch has not started)
-        }
-#ifdef ILQR_PK_DEBUG_HOOK      // phase-timing hook of tools/packed_phases.py (see ilqr_device_packed.hpp); never compiled into the product library
-        if (const char* dbg = std::getenv("ILQR_PK_DEBUG")) a.stage = std::atoi(dbg);
-#endif
-        // two waves per pack (a linearisation server beside the solver wave) while the batch leaves every SIMD at most two waves and
-        // a CU's LDS holds the second chunk buffers: up to 4 workgroups per CU (variant 5 = one wave per pack, 6 = two where they fit)
-        const int packs = (h->B + 3) / 4, cus = std::max(1, h->num_simds / 4), per_cu = (packs + cus - 1) / cus;
-        a.stage_flag = (h->variant != 5 && packed2_fits(h->vt->packed2_lds_bytes, per_cu)) ? 2 : 0;
-        a.stage_param = (double)per_cu;
-        {   // two-wave form: one solver wave per SIMD (KArgs::cu_slots; the one-wave form ignores it)
-            static const bool role_slots = !(std::getenv("ILQR_ROLE_SLOTS") && std::getenv("ILQR_ROLE_SLOTS")[0] == '0');
-            if (h->cu_slots != nullptr && role_slots && a.stage_flag == 2) {
-                HIP_TRY(hipMemsetAsync(h->cu_slots, 0, sizeof(int) * ilqr::CU_SLOT_INTS * ilqr::CU_SLOT_CUS, h->stream));
-                a.cu_slots = h->cu_slots; a.cu_expect = std::min(4, per_cu);
-            }
-        }
-        if (h->vt->launch_solve_packed(&a, h->stream) != 0) return drop(fail(ILQR_ERR_HIP, "solve (packed variant) launch failed"));
-        a.cu_slots = nullptr; a.cu_expect = 0;
-        a.stage_flag = 0; a.stage_param = 0.0; a.pool = nullptr; a.pool_mark = 0;
-        if (ho > 0 || live > 0) {
-            ilqr::KArgs r = a;
-            r.resume = 1; r.stage = 0;
-            if (h->vt->launch_solve(&r, h->lds_bytes, h->stream) != 0) return drop(fail(ILQR_ERR_HIP, "solve (hand-over resume) launch failed"));
-        }
-    } else if (slim) {
-        if (h->vt->launch_solve_slim(&a, (size_t)h->L.lds_doubles_slim * 8, h->stream) != 0)
-            return drop(fail(ILQR_ERR_HIP, "solve (throughput variant) launch failed"));
-    } else if (use_mid(h)) {
-        size_t lds_mid = h->lds_bytes;
-#ifdef ILQR_DBG_LDS_PAD_HOOK   // residency experiment of tools/mid_bench.py (more LDS per workgroup = fewer workgroups per CU); never in the product library
-        if (const char* pad = std::getenv("ILQR_DBG_LDS_PAD")) lds_mid += (size_t)std::atoi(pad);
-#endif
-        if (h->vt->launch_solve_mid(&a, lds_mid, h->stream) != 0) return drop(fail(ILQR_ERR_HIP, "solve (one-wave variant) launch failed"));
-    } else {
-        // two-wave latency kernel: one critical wave per SIMD (KArgs::cu_slots; ILQR_ROLE_SLOTS=0 leaves the roles as launched: A/B runs)
-        static const bool role_slots = !(std::getenv("ILQR_ROLE_SLOTS") && std::getenv("ILQR_ROLE_SLOTS")[0] == '0');
-        if (h->cu_slots != nullptr && role_slots) {
-            HIP_TRY(hipMemsetAsync(h->cu_slots, 0, sizeof(int) * ilqr::CU_SLOT_INTS * ilqr::CU_SLOT_CUS, h->stream));
-            const int cus = std::max(1, h->num_simds / 4);
-            a.cu_slots = h->cu_slots; a.cu_expect = std::min(4, (h->B + cus - 1) / cus);
-        }
-        if (h->vt->launch_solve(&a, h->lds_bytes, h->stream) != 0) return drop(fail(ILQR_ERR_HIP, "solve launch failed"));
+    const ilqr::LaunchPlan p = ilqr::solve_plan(launch_in(h));
+    if (p.kernel == 0) return drop(fail(ILQR_ERR_LDS, "this horizon only runs on the packed kernel"));
+    a.handover_outer = p.handover_outer; a.handover_live = p.handover_live;
+    ilqr::KArgs r = a;
+    r.resume = 1;                                     // the resume launch that finishes the instances handed over
+    if (p.handover_live > 0) HIP_TRY(hipMemsetAsync(h->done_counter, 0, sizeof(int), h->stream));
+    if (p.zero_pool) {
+        HIP_TRY(hipMemsetAsync(h->pool, 0, sizeof(int) * (size_t)(ilqr::POOL_Q + h->B + ilqr::POOL_CUS), h->stream));
+        h->pool_valid = true;
     }
+    a.pool = p.pool ? h->pool : nullptr;
+    a.pool_mark = p.pool_mark; a.pool_lds = p.pool_lds; a.pool_ctl = p.pool_ctl; a.pool_cu = p.pool_cu;
+    if (p.role_slots) {
+        HIP_TRY(hipMemsetAsync(h->cu_slots, 0, sizeof(int) * ilqr::CU_SLOT_INTS * ilqr::CU_SLOT_CUS, h->stream));
+        a.cu_slots = h->cu_slots; a.cu_expect = p.cu_expect;
+    }
+    size_t lds = p.lds;
+#ifdef ILQR_PK_DEBUG_HOOK      // phase-timing hook of tools/packed_phases.py (see ilqr_device_packed.hpp); never compiled into the product library
+    if (const char* dbg = std::getenv("ILQR_PK_DEBUG"); dbg && (p.kernel == ilqr::K_PACKED1 || p.kernel == ilqr::K_PACKED2)) a.stage = std::atoi(dbg);
+#endif
+#ifdef ILQR_DBG_LDS_PAD_HOOK   // residency experiment of tools/mid_bench.py (more LDS per workgroup = fewer workgroups per CU); never in the product library
+    if (const char* pad = std::getenv("ILQR_DBG_LDS_PAD"); pad && p.kernel == ilqr::K_MID) lds += (size_t)std::atoi(pad);
+#endif
+    if (h->vt->launch(p.kernel, &a, p.grid, lds, h->stream) != 0) return drop(fail(ILQR_ERR_HIP, "solve launch failed (kernel " + std::to_string(p.kernel) + ")"));
+    if (p.resume && h->vt->launch(ilqr::K_RESUME, &r, h->B, h->lds_bytes, h->stream) != 0)
+        return drop(fail(ILQR_ERR_HIP, "solve (hand-over resume) launch failed"));
     if (hipEventRecord(e1, h->stream) != hipSuccess) return drop(fail(ILQR_ERR_HIP, "hipEventRecord failed"));
     h->timing.emplace_back(e0, e1);
     if (h->timing.size() > 4096) {     // long-running callers that never read the timing: keep the newest half
@@ -1307,17 +1257,12 @@ int ilqr_run_stage_param(ilqr_handle* h, int32_t stage, double param, int32_t fl
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_run_stage_param(s, stage, param, flag); }, true);
     HIP_TRY(hipSetDevice(h->device));
     { const int rc = settle_reset(h); if (rc != ILQR_OK) return rc; }
-    if (!h->lds_fits) return fail(ILQR_ERR_LDS, "stage kernels are LDS-resident: this horizon only runs through ilqr_solve (packed kernel)");
+    const ilqr::LaunchPlan p = ilqr::stage_plan(launch_in(h));
+    if (p.kernel == 0) return fail(ILQR_ERR_LDS, "stage kernels are LDS-resident: this horizon only runs through ilqr_solve (packed kernel)");
     ilqr::KArgs a = make_args(h);
     a.stage = stage; a.stage_param = param; a.stage_flag = flag;
     if (stage != ILQR_STAGE_BACKWARD_PASS && stage != ILQR_STAGE_ILQR_SOLVE) a.qv = nullptr;
-    // the stage runs in the mapping selected by ilqr_set_kernel_variant (2 = throughput: one wave per instance)
-    if (h->variant == 2 && h->vt->launch_stage_slim != nullptr) {
-        if (h->vt->launch_stage_slim(&a, (size_t)h->L.lds_doubles_slim * 8, h->stream) != 0)
-            return fail(ILQR_ERR_HIP, "stage (throughput variant) launch failed");
-    } else if (h->variant == 4 && h->vt->launch_stage_mid != nullptr) {
-        if (h->vt->launch_stage_mid(&a, h->lds_bytes, h->stream) != 0) return fail(ILQR_ERR_HIP, "stage (one-wave variant) launch failed");
-    } else if (h->vt->launch_stage(&a, h->lds_bytes, h->stream) != 0) return fail(ILQR_ERR_HIP, "stage launch failed");
+    if (h->vt->launch(p.kernel, &a, p.grid, p.lds, h->stream) != 0) return fail(ILQR_ERR_HIP, "stage launch failed (kernel " + std::to_string(p.kernel) + ")");
     if (h->vt->launch_mirror) h->full_stale = true;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
@@ -1502,31 +1447,23 @@ int ilqr_set_buffer(ilqr_handle* h, const char* name, const double* in) {
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_set_kernel_variant(s, variant); });
     if (!h || variant < 0 || variant > 6) return fail(ILQR_ERR_INVALID, "variant must be 0 (auto), 1 (latency), 2 (throughput), 3 (packed), 4 (one wave per instance of a large model), 5 / 6 (packed with one / two waves per pack)");
-    if (variant == 4 && h->vt->launch_solve_mid == nullptr)
+    if (variant == 4 && !has_kernel(h->vt, ilqr::K_MID))
         return fail(ILQR_ERR_INVALID, "the one-wave variant exists for large models with nx, nu <= 16 only");
-    if ((variant == 3 || variant == 5 || variant == 6) && h->vt->launch_solve_packed == nullptr)
+    if ((variant == 3 || variant == 5 || variant == 6) && !has_kernel(h->vt, ilqr::K_PACKED1))
         return fail(ILQR_ERR_INVALID, "the packed variant exists for small models (nx, nu <= 4) only");
     if ((variant == 1 || variant == 2) && !h->lds_fits)
         return fail(ILQR_ERR_LDS, "this horizon exceeds the LDS-resident kernels: only the packed variant can run it");
-    if (variant == 2 && h->vt->launch_solve_slim == nullptr)
+    if (variant == 2 && !has_kernel(h->vt, ilqr::K_SLIM))
         return fail(ILQR_ERR_INVALID, "the throughput variant exists for small models (nx, nu <= 4) only");
     h->variant = variant;
     return ILQR_OK;
 }
 
-// what ilqr_solve launches for this handle as it stands (variant, batch, horizon): the auto rules of ilqr_solve, stated once more
+// what ilqr_solve launches for this handle as it stands (variant, batch, horizon): the kernel of its launch plan
 int ilqr_resolved_kernel_variant(ilqr_handle* h, int32_t* variant) {
     if (!h || !variant) return fail(ILQR_ERR_INVALID, "null argument");
     if (SHARDED(h)) return ilqr_resolved_kernel_variant(h->shards[0], variant);
-    const bool can_pack = h->vt->launch_solve_packed != nullptr;
-    const bool packed = can_pack && (h->variant == 3 || h->variant == 5 || h->variant == 6 || !h->lds_fits || (h->variant == 0 && h->B > h->num_simds));
-    const bool slim = !packed && h->vt->launch_solve_slim != nullptr && (h->variant == 2 || (h->variant == 0 && h->B > h->num_simds));
-    if (packed) {
-        const int packs = (h->B + 3) / 4, cus = std::max(1, h->num_simds / 4), per_cu = (packs + cus - 1) / cus;
-        *variant = (h->variant != 5 && packed2_fits(h->vt->packed2_lds_bytes, per_cu)) ? 6 : 5;      // the launcher's own rule (packed2_fits)
-    } else if (slim) *variant = 2;
-    else if (use_mid(h)) *variant = 4;
-    else *variant = 1;
+    *variant = ilqr::solve_plan(launch_in(h)).kernel;
     return ILQR_OK;
 }
 

@@ -32,6 +32,7 @@
 #include "../../include/ilqr_hip.h"
 #include "ilqr_layout.hpp"
 #include "ilqr_math.hpp"
+#include "ilqr_launch_plan.hpp"
 #include "ilqr_ric_schedule.hpp"
 
 namespace ilqr {
@@ -2323,150 +2324,62 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-// the packed kernel's two-wave form fits: its workgroups' LDS at per_cu workgroups per CU (one rule for the launcher and for
-// ilqr_solve / ilqr_resolved_kernel_variant on the host)
-inline bool packed2_fits(int lds2_bytes, int per_cu) { return lds2_bytes > 0 && per_cu >= 1 && per_cu <= 4 && (long long)per_cu * (lds2_bytes + 512) <= 160ll * 1024; }
-#define ILQR_MODEL_ABI_VERSION 10   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 11   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
     const char* name;
     int nx, nu, nw, ncs, nct;
     unsigned long long ineq_s, ineq_t;
-    int (*launch_solve)(const ilqr::KArgs* a, size_t lds_bytes, void* stream);
-    int (*launch_stage)(const ilqr::KArgs* a, size_t lds_bytes, void* stream);
+    // the solve and stage kernels (ilqr::Kernel, ilqr_launch_plan.hpp), launched as the host's launch plan says; bit k of
+    // `kernels`: the module has kernel k
+    int (*launch)(int kernel, const ilqr::KArgs* a, int grid, size_t lds_bytes, void* stream);
+    unsigned kernels;
     int (*launch_init)(const ilqr::KArgs* a, void* stream);
-    int (*launch_solve_slim)(const ilqr::KArgs* a, size_t lds_bytes, void* stream);   // null for large models
-    int (*launch_stage_slim)(const ilqr::KArgs* a, size_t lds_bytes, void* stream);   // null for large models
-    int (*launch_solve_packed)(const ilqr::KArgs* a, void* stream);                   // four instances per wave, no LDS; null for large models
     // large models only (null otherwise): the compact representation the kernels stream — row lengths for make_layout and
     // the kernel that writes the host-visible full arrays from it (dir 0) or reads them back (dir 1)
     int jac_nvar, hess_nnz;
     int (*launch_mirror)(const ilqr::KArgs* a, int dir, void* stream);
-    // large models whose matrices are single 16x16 tiles (nx, nu <= 16), null otherwise: the one-wave-per-instance variant
-    int (*launch_solve_mid)(const ilqr::KArgs* a, size_t lds_bytes, void* stream);
-    int (*launch_stage_mid)(const ilqr::KArgs* a, size_t lds_bytes, void* stream);
-    // LDS bytes of a workgroup of the packed kernel's two-wave form (0: no packed kernel): launch_solve_packed takes that form
-    // when KArgs::stage_flag == 2 and per_cu * (this + 512) <= 160 KiB — the host asks for it under the same condition
-    int packed2_lds_bytes;
+    // packed kernel (0: none): LDS bytes of the two chunk buffers of a one-wave workgroup (its control words follow them), and of a
+    // workgroup of the two-wave form
+    int packed1_lds_bytes, packed2_lds_bytes;
 };
 
 namespace ilqr {
+static_assert(PK_CTL_BYTES == sizeof(int) * CTL_WORDS, "ilqr_launch_plan.hpp: the one-wave packed form's control words");
 template <class M>
 struct ModelModule {
-    static int launch_solve(const KArgs* a, size_t lds, void* stream) {
+    static int go(void (*kernel)(KArgs), int grid, int block, size_t lds, void* stream, const KArgs& a) {
         // dynamic LDS above the 64 KiB default needs the per-device function attribute
         // (set on every such launch: handles may live on different devices of one process)
         if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<M>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+            hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, (hipStream_t)stream, a);
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
+    static int launch(int k, const KArgs* a, int grid, size_t lds, void* stream) {
+        constexpr int W = 64 * waves_of<M>::value;
+        if (k == K_LATENCY) return go(solve_kernel<M>, grid, W, lds, stream, *a);
+        if (k == K_STAGE) return go(stage_kernel<M>, grid, W, lds, stream, *a);
+        if constexpr (!is_large<M>::value) {
+            if (k == K_SLIM) return go(solve_kernel_slim<M>, grid, 64, lds, stream, *a);
+            if (k == K_STAGE_SLIM) return go(stage_kernel<Slim<M>>, grid, 64, lds, stream, *a);
+        }
         if constexpr (packed_ok<M>::value) {         // hand-over exists where the packed kernel does
-            if (a->resume) {
-                if (lds > 64 * 1024 &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel_resume<M>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-                hipLaunchKernelGGL(solve_kernel_resume<M>, dim3(a->B), dim3(64 * waves_of<M>::value), lds, (hipStream_t)stream, *a);
-                return hipGetLastError() == hipSuccess ? 0 : -1;
-            }
+            if (k == K_PACKED1) return go(solve_kernel_packed<M, false>, grid, 128, lds, stream, *a);
+            if (k == K_PACKED2) return go(solve_kernel_packed<M, true>, grid, 128, lds, stream, *a);
+            if (k == K_RESUME) return go(solve_kernel_resume<M>, grid, W, lds, stream, *a);
         }
-        hipLaunchKernelGGL(solve_kernel<M>, dim3(a->B), dim3(64 * waves_of<M>::value), lds, (hipStream_t)stream, *a);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    static int launch_stage(const KArgs* a, size_t lds, void* stream) {
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&stage_kernel<M>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-        hipLaunchKernelGGL(stage_kernel<M>, dim3(a->B), dim3(64 * waves_of<M>::value), lds, (hipStream_t)stream, *a);
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    static int launch_solve_slim(const KArgs* a, size_t lds, void* stream) {
-        if constexpr (!is_large<M>::value) {
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel_slim<M>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-            hipLaunchKernelGGL(solve_kernel_slim<M>, dim3(a->B), dim3(64), lds, (hipStream_t)stream, *a);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        } else {
-            return -1;
-        }
-    }
-    static int launch_stage_slim(const KArgs* a, size_t lds, void* stream) {
-        if constexpr (!is_large<M>::value) {
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&stage_kernel<Slim<M>>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-            hipLaunchKernelGGL(stage_kernel<Slim<M>>, dim3(a->B), dim3(64), lds, (hipStream_t)stream, *a);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        } else {
-            return -1;
-        }
-    }
-    // KArgs::stage_flag == 2 asks for the two-wave form (a linearisation server beside the solver wave, ilqr_device_packed.hpp) with
-    // KArgs::stage_param = workgroups per CU at this batch size: taken when its two chunk buffers fit a CU's LDS at that residency
-    static int launch_solve_packed(const KArgs* a, void* stream) {
-        if constexpr (packed_ok<M>::value) {
-            constexpr size_t lds2 = sizeof(double) * pk::PkLds<M, true>::total;
-            const double per_cu = a->stage_param >= 1.0 ? a->stage_param : 1.0;
-            if (a->stage_flag == 2 && packed2_fits((int)lds2, (int)per_cu)) {
-                KArgs b = *a;
-                b.stage_flag = 0; b.stage_param = 0.0;
-                hipLaunchKernelGGL((solve_kernel_packed<M, true>), dim3((a->B + 3) / 4), dim3(128), lds2, (hipStream_t)stream, b);
-            } else {
-                // one-wave form: two packs per workgroup (four workgroups of 256-register waves per CU); with the pool where the
-                // latency solver's LDS fits without costing residency
-                KArgs b = *a;
-                b.stage_flag = 0; b.stage_param = 0.0;
-                constexpr size_t pack = sizeof(double) * ((pk::PkLds<M, false>::total + 1) & ~1);
-                size_t lds = 2 * pack;
-                const size_t cu = 160 * 1024, ctl = sizeof(int) * CTL_WORDS;
-                auto per = [&](size_t bytes) { const size_t k = cu / ((bytes + 511) & ~(size_t)511); return k < 4 ? k : 4; };
-                if (b.pool != nullptr && b.pool_lds > 0) {
-                    const size_t with_pool = lds > (size_t)b.pool_lds ? lds : (size_t)b.pool_lds;
-                    if (per(with_pool + ctl) >= per(lds + ctl)) lds = with_pool; else b.pool = nullptr;
-                } else b.pool = nullptr;
-                b.pool_ctl = (int)(lds / sizeof(double));
-                lds += ctl;
-                // marks, vacated CUs and waiting workers belong to launches whose workgroups are ALL resident (a waiting workgroup
-                // would hold the slots the next round needs): with fewer than that resident — long horizons, per() < 4 — nobody is
-                // marked and nobody waits (advisor finding, round 5: the host's test assumed four workgroups per CU)
-                {
-                    int dev = 0, cus = 0;
-                    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-                    const size_t wgs = (size_t)(((a->B + 3) / 4 + 1) / 2);
-                    if (per(lds) * (size_t)cus < wgs) { b.pool_cu = 0; b.pool_mark = 0; }
-                }
-                if (lds > 64 * 1024 &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel_packed<M, false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-                hipLaunchKernelGGL((solve_kernel_packed<M, false>), dim3(((a->B + 3) / 4 + 1) / 2), dim3(128), lds, (hipStream_t)stream, b);
-            }
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        } else {
-            return -1;
-        }
-    }
-    static int launch_solve_mid(const KArgs* a, size_t lds, void* stream) {
         if constexpr (mid_ok<M>::value) {
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<Mid<M>>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-            hipLaunchKernelGGL(solve_kernel<Mid<M>>, dim3(a->B), dim3(64), lds, (hipStream_t)stream, *a);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        } else {
-            return -1;
+            if (k == K_MID) return go(solve_kernel<Mid<M>>, grid, 64, lds, stream, *a);
+            if (k == K_STAGE_MID) return go(stage_kernel<Mid<M>>, grid, 64, lds, stream, *a);
         }
+        return -1;
     }
-    static int launch_stage_mid(const KArgs* a, size_t lds, void* stream) {
-        if constexpr (mid_ok<M>::value) {
-            if (lds > 64 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(&stage_kernel<Mid<M>>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
-            hipLaunchKernelGGL(stage_kernel<Mid<M>>, dim3(a->B), dim3(64), lds, (hipStream_t)stream, *a);
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        } else {
-            return -1;
-        }
-    }
+    static constexpr unsigned kernels = 1u << K_LATENCY | 1u << K_STAGE |
+                                        (is_large<M>::value ? 0u : 1u << K_SLIM | 1u << K_STAGE_SLIM) |
+                                        (packed_ok<M>::value ? 1u << K_PACKED1 | 1u << K_PACKED2 | 1u << K_RESUME : 0u) |
+                                        (mid_ok<M>::value ? 1u << K_MID | 1u << K_STAGE_MID : 0u);
     static int launch_init(const KArgs* a, void* stream) {
         if constexpr (is_large<M>::value) hipLaunchKernelGGL(init_rollout_large_kernel<M>, dim3(a->B), dim3(64), 0, (hipStream_t)stream, *a);
         else hipLaunchKernelGGL(init_rollout_kernel<M>, dim3((a->B + 63) / 64), dim3(64), 0, (hipStream_t)stream, *a);
@@ -2480,19 +2393,16 @@ struct ModelModule {
             return -1;
         }
     }
+    template <class MM = M> static constexpr int packed1_lds() { if constexpr (packed_ok<MM>::value) return (int)(2 * sizeof(double) * ((pk::PkLds<MM, false>::total + 1) & ~1)); else return 0; }
     template <class MM = M> static constexpr int packed2_lds() { if constexpr (packed_ok<MM>::value) return (int)(sizeof(double) * pk::PkLds<MM, true>::total); else return 0; }
     template <class MM = M> static constexpr int jac_nvar() { if constexpr (is_large<MM>::value) return MM::JAC_NVAR; else return 0; }
     template <class MM = M> static constexpr int hess_nnz() { if constexpr (is_large<MM>::value) return MM::HESS_NXX + MM::HESS_NUU + MM::HESS_NUX; else return 0; }
     static const ilqr_model_vtable* vtable() {
         static const ilqr_model_vtable vt = {ILQR_MODEL_ABI_VERSION, (int)sizeof(KArgs),
                                              M::NAME, M::NX, M::NU, M::NW, M::NCS, M::NCT, M::INEQ_S, M::INEQ_T,
-                                             &launch_solve, &launch_stage, &launch_init,
-                                             is_large<M>::value ? nullptr : &launch_solve_slim,
-                                             is_large<M>::value ? nullptr : &launch_stage_slim,
-                                             packed_ok<M>::value ? &launch_solve_packed : nullptr,
+                                             &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
-                                             mid_ok<M>::value ? &launch_solve_mid : nullptr, mid_ok<M>::value ? &launch_stage_mid : nullptr,
-                                             packed2_lds<M>()};
+                                             packed1_lds<M>(), packed2_lds<M>()};
         return &vt;
     }
 };
