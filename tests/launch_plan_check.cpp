@@ -18,6 +18,7 @@ static const unsigned LARGE = 1u << K_LATENCY | 1u << K_STAGE;
 static const Model acrobot101 = {"acrobot T=101", SMALL, 28960, 28912, 39424, 20352};
 static const Model acrobot201 = {"acrobot T=201", SMALL, 28960, 28912, 75424, 40352};
 static const Model acrobot501 = {"acrobot T=501", SMALL, 28960, 28912, 183424, 100352};     // beyond the 160 KiB of a CU
+static const Model acrobot51 = {"acrobot T=51", SMALL, 28960, 28912, 21424, 10352};
 static const Model car51 = {"car T=51", SMALL, 22752, 22736, 28624, 19552};
 static const Model synth12 = {"synth12 T=101", MID, 0, 0, 25008, 138944};
 static const Model synth32 = {"synth32 T=101", LARGE, 0, 0, 61440, 0};
@@ -133,6 +134,16 @@ int main() {
     check("synth32 T=101 B=512 auto", solve_plan(in(synth32, 512)), plain(K_LATENCY, 512, 61440));
     // a small model without the packed kernel: the throughput kernel beyond #SIMDs
     check("no packed kernel B=4096 auto", solve_plan(in(nopack, 4096)), plain(K_SLIM, 4096, 20352));
+
+    // ---- both sides of auto's boundaries at 256 CUs (S = 1024 SIMDs), as tests/test_gpu_parity.py::test_auto_boundary_kernels_against_the_oracle
+    // solves them on the device: acrobot T=51 at S | S + 1 (latency | packed, two waves per pack: 257 packs, 2 per CU, live = B / 4),
+    // car T=51 at 16 C | 16 C + 4 (per-CU packs 4 -> 5: the one-wave form, 513 workgroups, the pool with the latency solver's 28 KB
+    // beside the packs at 4 workgroups per CU, all resident) and synth12 at 2 S | 2 S + 1 (rows above: latency | mid)
+    check("acrobot T=51 B=1024 auto (S)", solve_plan(in(acrobot51, 1024)), plain(K_LATENCY, 1024, 21424, 4));
+    check("acrobot T=51 B=1025 auto (S + 1)", solve_plan(in(acrobot51, 1025)),
+          {K_PACKED2, 257, 28912, 0, 256, true, true, 6, 1, 0, 21424, true, 2, true});
+    check("car T=51 B=4100 auto (16 C + 4)", solve_plan(in(car51, 4100)),
+          {K_PACKED1, 513, 28624 + 64, 0, 1024, true, true, 6, 1, 28624 / 8, 28624, false, 0, true});
 
     // ---- explicit variants, acrobot T=101 at 1024 (hand-over by head count: live = 256)
     check("acrobot T=101 B=1024 variant 1", solve_plan(in(acrobot101, 1024, 1)), plain(K_LATENCY, 1024, 39424, 4));
