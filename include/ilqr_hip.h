@@ -192,6 +192,32 @@ int ilqr_get_policy(ilqr_handle* h, double* K, double* k);
 /* solver.data.* — one record per instance. */
 int ilqr_get_stats(ilqr_handle* h, ilqr_stats* stats);
 
+/* Closed-loop rollouts of the handle's CURRENT policy (K_t, k_t) around its nominal trajectory (x̄, ū), from `samples` initial
+ * states per instance — rollout!(policy, problem; step_size), src/rollout.jl:1-31, started anywhere instead of at x̄_1:
+ *     x_1 = x1[b][s],   u_t = ū_t + K_t (x_t − x̄_t) + step_size k_t,   x_{t+1} = f(x_t, u_t, w_t)
+ * in the reference's operation order (src/rollout.jl:24-28); step_size = 0 is pure tracking, x1 = x̄_1 with step_size > 0 is the
+ * reference's rollout!. w_t: the handle's parameters, or the sample's own w[b][s][t] (the user's columns; a lowered problem's
+ * selector columns stay the handle's). Per sample: cost = the plain objective Σ cost (src/costs.jl:48-55, not the
+ * augmented-Lagrangian merit); max_violation = constraint_violation over the sample's trajectory (src/data/constraints.jl:23-39;
+ * 0 on a handle created unconstrained); first_nonfinite = −1, or the first 0-based t at which a component of x[b][s][t] is not
+ * finite (from there on that sample's outputs are unspecified; other samples are unaffected); optionally the trajectories.
+ * The call READS the handle: workspace, scalars, statistics, trace, timing and resident inputs are unchanged, a later solve behaves
+ * as if the call had not happened. Refused (ILQR_ERR_INVALID) without touching the GPU: samples < 1, null x1 or cost, w on a model
+ * without parameters, a handle that holds no policy yet (no solve, no backward-pass stage, no host write of K / k since the
+ * last reset). Host form: stages through device buffers the handle owns and reuses; on a sharded handle every instance's samples
+ * go to the device that owns the instance. Device form: every pointer a device pointer on the handle's device, asynchronous on
+ * the handle's stream; refused on a sharded handle. */
+int ilqr_rollout_policy(ilqr_handle* h, int32_t samples, double step_size,
+                        const double* x1,            /* [B][S][nx] */
+                        const double* w,             /* NULL, or [B][S][T][nw] */
+                        double* cost,                /* [B][S] */
+                        double* max_violation,       /* NULL, or [B][S] */
+                        int32_t* first_nonfinite,    /* NULL, or [B][S] */
+                        double* x,                   /* NULL, or [B][S][T][nx] */
+                        double* u);                  /* NULL, or [B][S][T-1][nu] */
+int ilqr_rollout_policy_device(ilqr_handle* h, int32_t samples, double step_size, const double* d_x1, const double* d_w, double* d_cost,
+                               double* d_max_violation, int32_t* d_first_nonfinite, double* d_x, double* d_u);
+
 /* Raw workspace access by reference field name (parity tests):
  * "nominal_states","nominal_actions","states","actions","jacobian_state",
  * "jacobian_action","gradient_state","gradient_action","hessian_state_state",

@@ -127,6 +127,9 @@ SYMBOLS = {
     "ilqr_get_trajectory": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "ilqr_get_policy": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "ilqr_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
+    "ilqr_rollout_policy": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
+                                      C.POINTER(C.c_int32), c_double_p, c_double_p]),
+    "ilqr_rollout_policy_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 7),
     "ilqr_buffer_len": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t)]),
     "ilqr_get_buffer": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p]),
     "ilqr_set_buffer": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p]),

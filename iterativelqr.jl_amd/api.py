@@ -258,6 +258,42 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_get_policy(self._h, _p(K), _p(k)))
         return K, k
 
+    def rollout_policy(self, x1, w=None, step_size=0.0, trajectories=False):
+        """Closed-loop rollouts of the current policy from x1[b, s] (ilqr_rollout_policy): u_t = ū_t + K_t (x_t − x̄_t) + step_size k_t,
+        S samples per instance, optionally under the samples' own parameters w[b, s, t]. Returns a dict with cost [B, S] (the plain
+        objective), max_violation [B, S], first_nonfinite [B, S] (−1, or the first 0-based t with a non-finite state) and, with
+        trajectories=True, x [B, S, T, nx] and u [B, S, T-1, nu]. Reads the handle; changes none of its state."""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64)
+        if x1.ndim < 2 or x1.shape[0] != self.B or x1.size % (self.B * self.nx) != 0:
+            raise ValueError("x1 must have shape [B, S, nx]")
+        S = x1.size // (self.B * self.nx)
+        x1 = x1.reshape(self.B, S, self.nx)
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float64)
+            if self.nw > 0:
+                w = w.reshape(self.B, S, self.T, self.nw)
+        out = dict(cost=np.empty((self.B, S)), max_violation=np.empty((self.B, S)), first_nonfinite=np.empty((self.B, S), dtype=np.int32))
+        if trajectories:
+            out["x"] = np.empty((self.B, S, self.T, self.nx)); out["u"] = np.empty((self.B, S, self.T - 1, self.nu))
+        _ffi.check(_ffi.lib().ilqr_rollout_policy(self._h, S, float(step_size), _p(x1), _p(w) if w is not None else None, _p(out["cost"]),
+                                                  _p(out["max_violation"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  _p(out["x"]) if trajectories else None, _p(out["u"]) if trajectories else None))
+        return out
+
+    def rollout_policy_device(self, samples, d_x1_ptr, d_cost_ptr, d_w_ptr=None, step_size=0.0, d_max_violation_ptr=None,
+                              d_first_nonfinite_ptr=None, d_x_ptr=None, d_u_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not wanted); asynchronous on the handle's stream."""
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_rollout_policy_device(self._h, int(samples), float(step_size), vp(d_x1_ptr), vp(d_w_ptr), vp(d_cost_ptr),
+                                                         vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr), vp(d_x_ptr), vp(d_u_ptr)))
+
+    def stream_ptr(self):
+        """The handle's HIP stream as an integer (ilqr_get_stream), e.g. for torch.cuda.ExternalStream; not on a sharded handle."""
+        s = C.c_void_p()
+        _ffi.check(_ffi.lib().ilqr_get_stream(self._h, C.byref(s)))
+        return s.value or 0
+
     def stats(self):
         st = (_ffi.Stats * self.B)()
         _ffi.check(_ffi.lib().ilqr_get_stats(self._h, st))

@@ -133,6 +133,10 @@ struct ilqr_handle {
     // the LAST n_sel parameter columns of every instance, the caller's ilqr_set_parameters fills the first nw - n_sel
     std::vector<double> sel;
     int n_sel = 0;
+    // ilqr_rollout_policy: K, k hold a policy (a solve, a backward-pass stage or a host write of K / k since the last reset), and the
+    // device staging of its host form — x1, w, cost, max_violation, first_nonfinite, x, u — which grows on demand and is reused
+    bool has_policy = false;
+    struct Stage { void* p = nullptr; size_t cap = 0; } pol[7];
 };
 
 namespace {
@@ -1048,6 +1052,7 @@ int ilqr_destroy(ilqr_handle* h) {
     if (h->pool) hipFree(h->pool);
     if (h->cu_slots) hipFree(h->cu_slots);
     if (h->d_u) hipFree(h->d_u);
+    for (auto& st : h->pol) if (st.p) hipFree(st.p);
     if (h->trace) hipFree(h->trace);
     if (h->qv) hipFree(h->qv);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1079,6 +1084,7 @@ int ilqr_reset(ilqr_handle* h) {
     if (!h) return fail(ILQR_ERR_INVALID, "null handle");
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_reset(s); });
     HIP_TRY(hipSetDevice(h->device));
+    h->has_policy = false;                            // K, k are zeroed below
     if (ilqr::is_large_model(h->vt->nx, h->vt->nu) && h->vt->nw == 0) {
         // HBM-resident models: zero the trajectories, gradients, gains, duals, scalars and the compact Jacobian / Hessian rows
         // now; the megabyte-sized full Jacobian / Hessian mirrors are rewritten from the compact form when a getter asks
@@ -1242,6 +1248,7 @@ int ilqr_solve(ilqr_handle* h) {
     if (p.resume && h->vt->launch(ilqr::K_RESUME, &r, h->B, h->lds_bytes, h->stream) != 0)
         return drop(fail(ILQR_ERR_HIP, "solve (hand-over resume) launch failed"));
     if (hipEventRecord(e1, h->stream) != hipSuccess) return drop(fail(ILQR_ERR_HIP, "hipEventRecord failed"));
+    h->has_policy = true;
     h->timing.emplace_back(e0, e1);
     if (h->timing.size() > 4096) {     // long-running callers that never read the timing: keep the newest half
         for (size_t i = 0; i < 2048; ++i) { hipEventDestroy(h->timing[i].first); hipEventDestroy(h->timing[i].second); }
@@ -1264,6 +1271,7 @@ int ilqr_run_stage_param(ilqr_handle* h, int32_t stage, double param, int32_t fl
     if (stage != ILQR_STAGE_BACKWARD_PASS && stage != ILQR_STAGE_ILQR_SOLVE) a.qv = nullptr;
     if (h->vt->launch(p.kernel, &a, p.grid, p.lds, h->stream) != 0) return fail(ILQR_ERR_HIP, "stage launch failed (kernel " + std::to_string(p.kernel) + ")");
     if (h->vt->launch_mirror) h->full_stale = true;
+    if (stage == ILQR_STAGE_BACKWARD_PASS || stage == ILQR_STAGE_ILQR_SOLVE || stage == ILQR_STAGE_SS_FINISH) h->has_policy = true;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
 }
@@ -1441,7 +1449,79 @@ int ilqr_set_buffer(ilqr_handle* h, const char* name, const double* in) {
     }
     const BufferDesc* bd = find_buffer(h, name);
     if (!bd) return fail(ILQR_ERR_INVALID, std::string("unknown buffer '") + name + "'");
-    return copy_in(h, bd, in);
+    const int rc = copy_in(h, bd, in);
+    if (rc == ILQR_OK && (bd->offset == h->L.K || bd->offset == h->L.k)) h->has_policy = true;      // the caller's own policy
+    return rc;
+}
+
+// ---- closed-loop rollouts of the handle's policy from the caller's initial states (ilqr_device_policy.hpp)
+// everything that can be refused without touching the GPU
+static int policy_check(const ilqr_handle* h, int32_t samples, const double* x1, const double* w, const double* cost, const char* who) {
+    const std::string me(who);
+    if (samples < 1) return fail(ILQR_ERR_INVALID, me + ": samples must be >= 1");
+    if (!x1) return fail(ILQR_ERR_INVALID, me + ": null x1");
+    if (!cost) return fail(ILQR_ERR_INVALID, me + ": null cost");
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (w && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w given, but this model has no parameters (num_parameter == 0)");
+    bool pol = h->has_policy;
+    if (!h->shards.empty()) { pol = true; for (const ilqr_handle* s : h->shards) pol = pol && s->has_policy; }
+    if (!pol) return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
+    return ILQR_OK;
+}
+
+static int policy_launch(ilqr_handle* h, int32_t samples, double step_size, const double* x1, const double* w, double* cost,
+                         double* max_violation, int32_t* first_nonfinite, double* x, double* u) {
+    if (!h->vt->launch_policy_rollout) return fail(ILQR_ERR_MODEL, "this model module has no policy rollout kernel");
+    ilqr::PolicyArgs a;
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = samples; a.constrained = h->constrained; a.n_sel = h->n_sel;
+    a.waves = (samples + 63) / 64 > 4 ? 4 : (samples + 63) / 64;
+    a.alpha = step_size; a.x1 = x1; a.w = w; a.cost = cost; a.viol = max_violation; a.nonfinite = first_nonfinite; a.x = x; a.u = u;
+    if (h->vt->launch_policy_rollout(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "policy rollout launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_rollout_policy_device(ilqr_handle* h, int32_t samples, double step_size, const double* x1, const double* w, double* cost,
+                               double* max_violation, int32_t* first_nonfinite, double* x, double* u) {
+    const int rc = policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy_device");
+    if (rc != ILQR_OK) return rc;
+    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_rollout_policy (host pointers) on a sharded handle");
+    HIP_TRY(hipSetDevice(h->device));
+    return policy_launch(h, samples, step_size, x1, w, cost, max_violation, first_nonfinite, x, u);
+}
+
+int ilqr_rollout_policy(ilqr_handle* h, int32_t samples, double step_size, const double* x1, const double* w, double* cost,
+                        double* max_violation, int32_t* first_nonfinite, double* x, double* u) {
+    int rc = policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy");
+    if (rc != ILQR_OK) return rc;
+    const size_t S = (size_t)samples, T = (size_t)h->L.T, N = T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        const size_t o = lo * S;
+        return ilqr_rollout_policy(s, samples, step_size, x1 + o * n, w ? w + o * T * nwu : nullptr, cost + o, max_violation ? max_violation + o : nullptr,
+                                   first_nonfinite ? first_nonfinite + o : nullptr, x ? x + o * T * n : nullptr, u ? u + o * N * m : nullptr); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t BS = (size_t)h->B * S;
+    const size_t bytes[7] = {BS * n * 8, w ? BS * T * nwu * 8 : 0, BS * 8, max_violation ? BS * 8 : 0, first_nonfinite ? BS * 4 : 0,
+                             x ? BS * T * n * 8 : 0, u ? BS * N * m * 8 : 0};
+    void* d[7];
+    for (int i = 0; i < 7; ++i) {
+        ilqr_handle::Stage& st = h->pol[i];
+        if (bytes[i] > st.cap) {
+            HIP_TRY(hipStreamSynchronize(h->stream));
+            if (st.p) { HIP_TRY(hipFree(st.p)); st.p = nullptr; st.cap = 0; }
+            HIP_TRY(hipMalloc(&st.p, bytes[i]));
+            st.cap = bytes[i];
+        }
+        d[i] = bytes[i] ? st.p : nullptr;
+    }
+    HIP_TRY(hipMemcpyAsync(d[0], x1, bytes[0], hipMemcpyHostToDevice, h->stream));
+    if (w) HIP_TRY(hipMemcpyAsync(d[1], w, bytes[1], hipMemcpyHostToDevice, h->stream));
+    rc = policy_launch(h, samples, step_size, (const double*)d[0], (const double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (double*)d[5], (double*)d[6]);
+    if (rc != ILQR_OK) return rc;
+    void* host[7] = {nullptr, nullptr, cost, max_violation, first_nonfinite, x, u};
+    for (int i = 2; i < 7; ++i)
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ILQR_OK;
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

@@ -2321,10 +2321,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 
 }  // namespace ilqr
 #include "ilqr_device_packed.hpp"
+#include "ilqr_device_policy.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 11   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 12   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2343,6 +2344,8 @@ extern "C" struct ilqr_model_vtable {
     // packed kernel (0: none): LDS bytes of the two chunk buffers of a one-wave workgroup (its control words follow them), and of a
     // workgroup of the two-wave form
     int packed1_lds_bytes, packed2_lds_bytes;
+    // closed-loop rollouts of the handle's policy from the caller's initial states (ilqr_device_policy.hpp): reads the workspace only
+    int (*launch_policy_rollout)(const ilqr::PolicyArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2402,7 +2405,7 @@ struct ModelModule {
                                              M::NAME, M::NX, M::NU, M::NW, M::NCS, M::NCT, M::INEQ_S, M::INEQ_T,
                                              &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
-                                             packed1_lds<M>(), packed2_lds<M>()};
+                                             packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>};
         return &vt;
     }
 };

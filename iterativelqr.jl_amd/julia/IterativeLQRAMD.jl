@@ -14,7 +14,7 @@
 module IterativeLQRAMD
 
 export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!,
-       set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
+       set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 const LIB = Ref{String}(joinpath(@__DIR__, "..", "lib", "libilqr_hip.so"))
 
@@ -150,6 +150,24 @@ function get_policy(s::Solver)
     K = Array{Float64,4}(undef, s.nu, s.nx, s.T - 1, s.B); k = Array{Float64,3}(undef, s.nu, s.T - 1, s.B)
     check(ccall((:ilqr_get_policy, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.handle, K, k))
     return K, k
+end
+
+# Closed-loop rollouts of the current policy from x1[:, s, b] (ilqr_rollout_policy): rollout!(policy, problem; step_size) of
+# src/rollout.jl:1-31 started at the caller's states, S samples per instance, optionally under the samples' own parameters
+# w[:, t, s, b]. Returns (cost, max_violation, first_nonfinite) as S×B arrays and, with trajectories = true, x (nx×T×S×B) and
+# u (nu×(T-1)×S×B) as well. The handle's state is not changed.
+function rollout_policy(s::Solver, x1::Array{Float64,3}; w::Union{Nothing,Array{Float64,4}} = nothing, step_size::Float64 = 0.0,
+                        trajectories::Bool = false)
+    S = size(x1, 2)
+    cost = Array{Float64,2}(undef, S, s.B); viol = Array{Float64,2}(undef, S, s.B); nonfinite = Array{Int32,2}(undef, S, s.B)
+    x = trajectories ? Array{Float64,4}(undef, s.nx, s.T, S, s.B) : nothing
+    u = trajectories ? Array{Float64,4}(undef, s.nu, s.T - 1, S, s.B) : nothing
+    nul = Ptr{Float64}(C_NULL)
+    check(ccall((:ilqr_rollout_policy, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, Int32(S), step_size, x1, w === nothing ? nul : w, cost, viol, nonfinite,
+                trajectories ? x : nul, trajectories ? u : nul))
+    return trajectories ? (cost, viol, nonfinite, x, u) : (cost, viol, nonfinite)
 end
 
 # solver.data.* per instance
