@@ -2,16 +2,10 @@
 // kernel launches on a private HIP stream, host<->device accessors.
 // No CPU fallback: without a HIP device ilqr_create fails loudly.
 #include <dlfcn.h>
-#include <spawn.h>
-#include <sys/stat.h>
-#include <sys/wait.h>
-#include <unistd.h>
 
-#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <fcntl.h>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -19,6 +13,7 @@
 #include <vector>
 
 #include "ilqr_device.hpp"
+#include "ilqr_host.hpp"
 
 namespace ilqr {
 // fresh-solver defaults after the workspace has been zero-filled:
@@ -67,11 +62,6 @@ namespace {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
@@ -84,15 +74,23 @@ std::vector<const ilqr_model_vtable*>& registry() {
     return r;
 }
 
-const ilqr_model_vtable* find_model(const char* name) {
+struct BufferDesc { const char* name; int offset; int len; };
+
+}  // namespace
+
+// what ilqr_host.hpp promises the model compiler (ilqr_model_compile.cpp)
+int ilqr::fail(int code, const std::string& msg) {
+    g_err = msg;
+    return code;
+}
+const ilqr_model_vtable* ilqr::find_model(const char* name) {
     for (auto* vt : registry())
         if (!std::strcmp(vt->name, name)) return vt;
     return nullptr;
 }
-
-struct BufferDesc { const char* name; int offset; int len; };
-
-}  // namespace
+long long ilqr::model_abi_word() { return ILQR_MODEL_ABI_VERSION * 1000 + (long long)sizeof(ilqr::KArgs); }
+using ilqr::fail;
+using ilqr::find_model;
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -388,367 +386,6 @@ int ilqr_register_model(const ilqr_model_vtable* vt) {
 }
 int ilqr_model_count(void) { return (int)registry().size(); }
 
-// ---- structure of a large model's callables, found by running them on the HOST (ilqr_compile_model)
-// The reference gets sparse, partly constant Jacobians and Hessians for free: Symbolics differentiates the user's function and
-// emits code for the non-trivial entries only (src/dynamics.jl:16-34, src/costs.jl:17-44). A C host hands over opaque callables;
-// what the large path streams per timestep (ilqr_device_large.hpp: state-dependent Jacobian entries, structurally non-zero
-// Hessian entries) is therefore found by PROBING: the source is compiled once more with the host compiler, every Jacobian /
-// Hessian / constraint-Jacobian callable is evaluated at three pseudo-random points, and an entry that comes out bitwise equal
-// at all of them is a constant (zero or not). A Hessian entry counts as structurally non-zero if a cost Hessian or a Gauss-Newton
-// term cxᵀ Iρ cx (src/gradients.jl:63-79) can put something there. Failing any step (no host compiler, source that does not
-// compile as host C++) is not an error: the dense tables are used, as before.
-struct ModelStructure {
-    bool found = false;
-    std::vector<double> fxc, fuc;          // constant Jacobian entries (0 where state-dependent)
-    std::vector<int> jac_var;              // indices into [fx | fu] of the state-dependent ones
-    std::vector<int> hess_idx, tile_start; // compact Hessian row: [gxx by 16x16 tile | guu | gux], indices inside each matrix
-    int nxx = 0, nuu = 0, nux = 0;
-    std::string note;
-};
-
-static int run_child(const std::vector<std::string>& args, const std::string& log) {
-    std::vector<const char*> argv;
-    for (auto& a : args) argv.push_back(a.c_str());
-    argv.push_back(nullptr);
-    posix_spawn_file_actions_t fa;
-    posix_spawn_file_actions_init(&fa);
-    posix_spawn_file_actions_addopen(&fa, 1, log.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-    posix_spawn_file_actions_adddup2(&fa, 1, 2);
-    pid_t pid = 0;
-    extern char** environ;
-    const int sp = posix_spawn(&pid, args[0].c_str(), &fa, nullptr, const_cast<char* const*>(argv.data()), environ);
-    posix_spawn_file_actions_destroy(&fa);
-    if (sp != 0) return -1;
-    int status = 0;
-    if (waitpid(pid, &status, 0) < 0 || !WIFEXITED(status)) return -1;
-    return WEXITSTATUS(status);
-}
-
-// selector columns of a lowered model (ilqr_compile_model_stages): the probe must visit every kind of every category
-struct ProbeHints { int sel[3] = {-1, -1, -1}; int kinds[3] = {0, 0, 0}; };
-
-static ModelStructure probe_model_structure(const ilqr_model_source* src, const std::string& dir, const std::string& tag, const ProbeHints& hints) {
-    ModelStructure ms;
-    const int n = src->nx, m = src->nu, nw = src->nw, ncs = src->nc_stage, nct = src->nc_term;
-    if (src->flags & ILQR_MODEL_DENSE_TABLES) { ms.note = "disabled for this model (ILQR_MODEL_DENSE_TABLES)"; return ms; }
-    if (std::getenv("ILQR_NO_STRUCTURE_PROBE")) { ms.note = "disabled by ILQR_NO_STRUCTURE_PROBE"; return ms; }
-    std::string cxx;
-    const char* cand[] = {std::getenv("ILQR_HOSTCXX"), "/usr/bin/g++", "/usr/bin/c++", "/usr/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++"};
-    for (const char* c : cand)
-        if (c && access(c, X_OK) == 0) { cxx = c; break; }
-    if (cxx.empty()) { ms.note = "no host C++ compiler (set ILQR_HOSTCXX)"; return ms; }
-    static std::atomic<unsigned> probe_seq{0};          // two threads of one process compiling the same model must not share temp files
-    const std::string pid = std::to_string((long)getpid()) + "_" + std::to_string(probe_seq.fetch_add(1));
-    const std::string cpp = dir + "/probe_" + tag + "." + pid + ".cpp", so = dir + "/probe_" + tag + "." + pid + ".so", log = dir + "/probe_" + tag + "." + pid + ".log";
-    FILE* f = std::fopen(cpp.c_str(), "w");
-    if (!f) { ms.note = "cannot write " + cpp; return ms; }
-    std::fprintf(f, "// GENERATED by ilqr_compile_model: the user's callables compiled for the host, to find constant / zero entries\n"
-                    "#include <cmath>\n#include <math.h>\n#define ILQR_MODEL_FN inline\nnamespace ilqr_user {\nusing namespace std;\n%s\n}\n"
-                    "extern \"C\" void ilqr_probe(int which, double* o, const double* x, const double* u, const double* w) {\n    switch (which) {\n"
-                    "        case 0: ilqr_user::dynamics_jacobian_state(o, x, u, w); break;\n        case 1: ilqr_user::dynamics_jacobian_action(o, x, u, w); break;\n"
-                    "        case 2: ilqr_user::cost_stage_hessian_state_state(o, x, u, w); break;\n        case 3: ilqr_user::cost_stage_hessian_action_action(o, x, u, w); break;\n"
-                    "        case 4: ilqr_user::cost_stage_hessian_action_state(o, x, u, w); break;\n        case 5: ilqr_user::cost_terminal_hessian_state_state(o, x, u, w); break;\n",
-                 src->source);
-    if (ncs > 0) std::fprintf(f, "        case 6: ilqr_user::constraint_stage_jacobian_state(o, x, u, w); break;\n        case 7: ilqr_user::constraint_stage_jacobian_action(o, x, u, w); break;\n");
-    if (nct > 0) std::fprintf(f, "        case 8: ilqr_user::constraint_terminal_jacobian_state(o, x, u, w); break;\n");
-    std::fprintf(f, "        default: break;\n    }\n}\n");
-    std::fclose(f);
-    const int rc = run_child({cxx, "-O1", "-std=c++17", "-fPIC", "-shared", "-w", cpp, "-o", so, "-lm"}, log);
-    auto cleanup = [&]() { std::remove(cpp.c_str()); std::remove(so.c_str()); std::remove(log.c_str()); };
-    if (rc != 0) { ms.note = "the source does not compile for the host (" + cxx + ", see " + log + ")"; std::remove(cpp.c_str()); return ms; }
-    void* hl = dlopen(so.c_str(), RTLD_NOW | RTLD_LOCAL);
-    typedef void (*probe_fn)(int, double*, const double*, const double*, const double*);
-    probe_fn pf = hl ? (probe_fn)dlsym(hl, "ilqr_probe") : nullptr;
-    if (!pf) { ms.note = "cannot load the host build of the callables"; if (hl) dlclose(hl); cleanup(); return ms; }
-    // 48 points: magnitudes 1e-3, 0.03, 1, 30, 1e3 per point (every argument of a point at the same scale, so that small and large
-    // regimes are each seen whole) and mixed scales per component on the rest, both signs; x, u and w alike. What this cannot
-    // see is a piecewise callable whose pieces have the same derivative on all of them: see ilqr_hip.h (ILQR_MODEL_DENSE_TABLES).
-    const int P = 48;
-    const int sizes[9] = {n * n, n * m, n * n, m * m, m * n, n * n, ncs * n, ncs * m, nct * n};
-    std::vector<std::vector<double>> val[9];
-    unsigned long long seed = 0x9E3779B97F4A7C15ull;
-    auto uni = [&]() { seed = seed * 6364136223846793005ull + 1442695040888963407ull; return (double)(seed >> 11) / 9007199254740992.0; };
-    const double scales[5] = {1.0e-3, 3.0e-2, 1.0, 30.0, 1.0e3};
-    for (int p = 0; p < P; ++p) {
-        std::vector<double> x(n), u(m), w(nw > 0 ? nw : 1);
-        auto draw = [&]() { const double sc = p < 30 ? scales[p % 5] : scales[(int)(uni() * 5.0) % 5]; return (uni() < 0.5 ? -1.0 : 1.0) * sc * (0.35 + 1.3 * uni()); };
-        for (auto& v : x) v = draw();
-        for (auto& v : u) v = draw();
-        for (auto& v : w) v = draw();
-        for (int c = 0; c < 3; ++c)                                  // one-hot selectors: every kind of every category in turn
-            for (int k = 0; k < hints.kinds[c]; ++k) w[hints.sel[c] + k] = (k == (p / (c == 0 ? 1 : (c == 1 ? 2 : 3))) % hints.kinds[c]) ? 1.0 : 0.0;
-        for (int k = 0; k < 9; ++k) {
-            std::vector<double> o((size_t)(sizes[k] > 0 ? sizes[k] : 1), 0.0);
-            const bool have = k < 6 || (k < 8 ? ncs > 0 : nct > 0);
-            if (have && sizes[k] > 0) pf(k, o.data(), x.data(), u.data(), w.data());       // (terminal objects see u of the stage size: ignored by them)
-            val[k].push_back(o);
-        }
-    }
-    dlclose(hl);
-    cleanup();
-    // a NaN / Inf compares bitwise equal to itself: such an entry is never a constant
-    auto same = [&](int k, int e) { for (int p = 0; p < P; ++p) if (!std::isfinite(val[k][p][e]) || std::memcmp(&val[k][p][e], &val[k][0][e], 8) != 0) return false; return true; };
-    auto nonzero = [&](int k, int e) { for (int p = 0; p < P; ++p) if (val[k][p][e] != 0.0 || val[k][p][e] != val[k][p][e]) return true; return false; };
-    ms.fxc.assign(n * n, 0.0); ms.fuc.assign(n * m, 0.0);
-    for (int e = 0; e < n * n; ++e) { if (same(0, e)) ms.fxc[e] = val[0][0][e]; else ms.jac_var.push_back(e); }
-    for (int e = 0; e < n * m; ++e) { if (same(1, e)) ms.fuc[e] = val[1][0][e]; else ms.jac_var.push_back(n * n + e); }
-    // Hessian pattern: cost Hessians (stage and terminal share the row) and the Gauss-Newton terms of every constraint row
-    std::vector<char> pxx(n * n, 0), puu(m * m, 0), pux(m * n, 0);
-    for (int e = 0; e < n * n; ++e) pxx[e] = nonzero(2, e) || nonzero(5, e);
-    for (int e = 0; e < m * m; ++e) puu[e] = nonzero(3, e);
-    for (int e = 0; e < m * n; ++e) pux[e] = nonzero(4, e);
-    auto gauss_newton = [&](int kx, int ku, int nc) {
-        for (int i = 0; i < nc; ++i) {
-            std::vector<int> sx, su;
-            for (int j = 0; j < n; ++j) if (nonzero(kx, j * nc + i)) sx.push_back(j);
-            if (ku >= 0) for (int j = 0; j < m; ++j) if (nonzero(ku, j * nc + i)) su.push_back(j);
-            for (int a : sx) for (int b : sx) pxx[a * n + b] = 1;
-            for (int a : su) for (int b : su) puu[a * m + b] = 1;
-            for (int a : sx) for (int b : su) pux[a * m + b] = 1;         // gux(i2, j) at j * m + i2: column j = state, row i2 = action
-        }
-    };
-    if (ncs > 0) gauss_newton(6, 7, ncs);
-    if (nct > 0) gauss_newton(8, -1, nct);
-    const int TN = (n + 15) / 16;
-    for (int tile = 0; tile < TN * TN; ++tile) {
-        ms.tile_start.push_back((int)ms.hess_idx.size());
-        for (int idx = 0; idx < n * n; ++idx) {
-            const int col = idx / n, row = idx % n;
-            if (pxx[idx] && (row / 16) * TN + col / 16 == tile) ms.hess_idx.push_back(idx);
-        }
-    }
-    ms.tile_start.push_back((int)ms.hess_idx.size());
-    ms.nxx = (int)ms.hess_idx.size();
-    for (int e = 0; e < m * m; ++e) if (puu[e]) { ms.hess_idx.push_back(e); ms.nuu++; }
-    for (int e = 0; e < m * n; ++e) if (pux[e]) { ms.hess_idx.push_back(e); ms.nux++; }
-    ms.found = true;
-    return ms;
-}
-
-// Dynamics / Cost / Constraint constructors for hosts without Python: C source of the reference's callables -> model module.
-// What the probe found, kept beside the modules under the PRE-probe hash (source, dimensions, ABI, kernel headers + flags) and the
-// probe hints: ilqr_compile_model[_rows,_stages] is called by every rank of a job and on every start of a host, and the probe —
-// a host compilation in a child process, a dlopen, 48 points x 9 callables — used to run every time although the module it
-// leads to was cached (advisor finding, round 5). Only a SUCCESSFUL probe is kept: where probing is impossible (no host
-// compiler, switched off) the answer is cheap and must not be served on a box where it would work.
-static ModelStructure probe_model_structure_cached(const ilqr_model_source* src, const std::string& dir, const std::string& tag, const ProbeHints& hints) {
-    if ((src->flags & ILQR_MODEL_DENSE_TABLES) || std::getenv("ILQR_NO_STRUCTURE_PROBE")) return probe_model_structure(src, dir, tag, hints);
-    unsigned long long hh = 1469598103934665603ull;
-    for (size_t i = 0; i < sizeof(hints); ++i) { hh ^= ((const unsigned char*)&hints)[i]; hh *= 1099511628211ull; }
-    char hb[24];
-    std::snprintf(hb, sizeof(hb), "%08llx", hh & 0xffffffffull);
-    const std::string path = dir + "/probe_" + tag + "_" + hb + ".bin";
-    const int n = src->nx, m = src->nu;
-    static const char magic[8] = {'I', 'L', 'Q', 'R', 'P', 'R', 'B', '1'};
-    if (FILE* f = std::fopen(path.c_str(), "rb")) {
-        ModelStructure ms;
-        char mg[8];
-        int hd[8];
-        bool ok = std::fread(mg, 1, 8, f) == 8 && std::memcmp(mg, magic, 8) == 0 && std::fread(hd, sizeof(int), 8, f) == 8 &&
-                  hd[0] == n && hd[1] == m && hd[5] >= 0 && hd[6] >= 0 && hd[7] >= 0 && hd[5] <= n * n + n * m && hd[6] <= n * n + m * m + m * n && hd[7] <= 64;
-        if (ok) {
-            ms.nxx = hd[2]; ms.nuu = hd[3]; ms.nux = hd[4];
-            ms.fxc.resize((size_t)n * n); ms.fuc.resize((size_t)n * m); ms.jac_var.resize(hd[5]); ms.hess_idx.resize(hd[6]); ms.tile_start.resize(hd[7]);
-            ok = std::fread(ms.fxc.data(), 8, ms.fxc.size(), f) == ms.fxc.size() && std::fread(ms.fuc.data(), 8, ms.fuc.size(), f) == ms.fuc.size() &&
-                 std::fread(ms.jac_var.data(), sizeof(int), ms.jac_var.size(), f) == ms.jac_var.size() &&
-                 std::fread(ms.hess_idx.data(), sizeof(int), ms.hess_idx.size(), f) == ms.hess_idx.size() &&
-                 std::fread(ms.tile_start.data(), sizeof(int), ms.tile_start.size(), f) == ms.tile_start.size() &&
-                 ms.nxx + ms.nuu + ms.nux == (int)ms.hess_idx.size();
-        }
-        std::fclose(f);
-        if (ok) { ms.found = true; ms.note = "structure from " + path; return ms; }
-    }
-    ModelStructure ms = probe_model_structure(src, dir, tag, hints);
-    if (ms.found && (int)ms.fxc.size() == n * n && (int)ms.fuc.size() == n * m) {
-        const std::string tmp = path + "." + std::to_string((long)getpid());
-        if (FILE* f = std::fopen(tmp.c_str(), "wb")) {
-            const int hd[8] = {n, m, ms.nxx, ms.nuu, ms.nux, (int)ms.jac_var.size(), (int)ms.hess_idx.size(), (int)ms.tile_start.size()};
-            bool ok = std::fwrite(magic, 1, 8, f) == 8 && std::fwrite(hd, sizeof(int), 8, f) == 8 &&
-                      std::fwrite(ms.fxc.data(), 8, ms.fxc.size(), f) == ms.fxc.size() && std::fwrite(ms.fuc.data(), 8, ms.fuc.size(), f) == ms.fuc.size() &&
-                      std::fwrite(ms.jac_var.data(), sizeof(int), ms.jac_var.size(), f) == ms.jac_var.size() &&
-                      std::fwrite(ms.hess_idx.data(), sizeof(int), ms.hess_idx.size(), f) == ms.hess_idx.size() &&
-                      std::fwrite(ms.tile_start.data(), sizeof(int), ms.tile_start.size(), f) == ms.tile_start.size();
-            ok = (std::fclose(f) == 0) && ok;
-            if (ok) std::rename(tmp.c_str(), path.c_str()); else std::remove(tmp.c_str());
-        }
-    }
-    return ms;
-}
-
-static int compile_model_impl(const ilqr_model_source* src, const uint64_t* ineq_stage_words, const uint64_t* ineq_term_words,
-                              char* registered_name, size_t name_len, char* library_path, size_t path_len, const ProbeHints& hints = ProbeHints());
-int ilqr_compile_model(const ilqr_model_source* src, char* registered_name, size_t name_len, char* library_path, size_t path_len) {
-    if (src && (src->nc_stage > 64 || src->nc_term > 64))
-        return fail(ILQR_ERR_INVALID, "ilqr_compile_model: at most 64 constraint rows per stage fit the 64-bit inequality masks — "
-                                      "ilqr_compile_model_rows takes the masks as arrays of words");
-    return compile_model_impl(src, nullptr, nullptr, registered_name, name_len, library_path, path_len);
-}
-int ilqr_compile_model_rows(const ilqr_model_source* src, const uint64_t* ineq_stage_words, const uint64_t* ineq_term_words,
-                            char* registered_name, size_t name_len, char* library_path, size_t path_len) {
-    if (src && ((src->nc_stage > 64 && !ineq_stage_words) || (src->nc_term > 64 && !ineq_term_words)))
-        return fail(ILQR_ERR_INVALID, "ilqr_compile_model_rows: more than 64 rows need their inequality words");
-    return compile_model_impl(src, ineq_stage_words, ineq_term_words, registered_name, name_len, library_path, path_len);
-}
-static int compile_model_impl(const ilqr_model_source* src, const uint64_t* ineq_stage_words, const uint64_t* ineq_term_words,
-                              char* registered_name, size_t name_len, char* library_path, size_t path_len, const ProbeHints& hints) {
-    if (!src || !src->name || !src->source || !registered_name || !library_path)
-        return fail(ILQR_ERR_INVALID, "null argument");
-    if (src->nx < 1 || src->nx > 64 || src->nu < 1 || src->nu > 16 || src->nw < 0 || src->nc_stage < 0 || src->nc_stage > ILQR_MAX_CONSTRAINT_ROWS ||
-        src->nc_term < 0 || src->nc_term > ILQR_MAX_CONSTRAINT_ROWS)
-        return fail(ILQR_ERR_INVALID, "ilqr_compile_model: 1 <= nx <= 64, 1 <= nu <= 16, at most 256 constraint rows per stage");
-    // inequality rows as words of 64 (the struct's masks are word 0 when no array is given)
-    const int nwords = std::max(1, (std::max(src->nc_stage, src->nc_term) + 63) / 64);
-    std::vector<uint64_t> iw_s(nwords, 0), iw_t(nwords, 0);
-    for (int k = 0; k < nwords; ++k) {
-        iw_s[k] = ineq_stage_words ? (k < (src->nc_stage + 63) / 64 ? ineq_stage_words[k] : 0) : (k == 0 ? src->ineq_stage : 0);
-        iw_t[k] = ineq_term_words ? (k < (src->nc_term + 63) / 64 ? ineq_term_words[k] : 0) : (k == 0 ? src->ineq_term : 0);
-    }
-    for (const char* c = src->name; *c; ++c)
-        if (!((*c >= 'a' && *c <= 'z') || (*c >= 'A' && *c <= 'Z') || (*c >= '0' && *c <= '9') || *c == '_'))
-            return fail(ILQR_ERR_INVALID, "model name must be a C identifier");
-    // where this library lives: <pkg>/lib/libilqr_hip.so, kernels in <pkg>/csrc (ILQR_CSRC_DIR overrides)
-    Dl_info di;
-    if (!dladdr((const void*)&ilqr_compile_model, &di) || !di.dli_fname) return fail(ILQR_ERR_MODEL, "cannot locate libilqr_hip.so");
-    std::string libdir(di.dli_fname);
-    libdir = libdir.substr(0, libdir.find_last_of('/'));
-    const char* env_csrc = std::getenv("ILQR_CSRC_DIR");
-    const std::string csrc = env_csrc ? env_csrc : libdir + "/../csrc";
-    const char* env_hipcc = std::getenv("ILQR_HIPCC");
-    const std::string hipcc = env_hipcc ? env_hipcc : "/opt/rocm/bin/hipcc";
-    // tag = FNV-1a over everything that ends up in the module: source, dimensions, ABI version and the hash of the kernel
-    // headers + compiler flags this library was built from (ILQR_BUILD_HASH, computed by the Makefile): a kernel fix without an
-    // ABI bump must not be served a module compiled against the old kernels
-    unsigned long long hsh = 1469598103934665603ull;
-    auto mix = [&](const void* p, size_t n) { for (size_t i = 0; i < n; ++i) { hsh ^= ((const unsigned char*)p)[i]; hsh *= 1099511628211ull; } };
-    mix(src->source, std::strlen(src->source)); mix(src->name, std::strlen(src->name));
-    const long long dims[8] = {src->nx, src->nu, src->nw, src->nc_stage, src->nc_term, (long long)iw_s[0], (long long)iw_t[0],
-                               ILQR_MODEL_ABI_VERSION * 1000 + (long long)sizeof(ilqr::KArgs)};
-    mix(dims, sizeof(dims));
-    if (nwords > 1) { mix(iw_s.data(), sizeof(uint64_t) * nwords); mix(iw_t.data(), sizeof(uint64_t) * nwords); }
-#ifdef ILQR_BUILD_HASH
-    mix(ILQR_BUILD_HASH, std::strlen(ILQR_BUILD_HASH));
-#endif
-    // The tables a large model is built with are part of its identity: the probe runs BEFORE the name is formed and what it
-    // found (or that it found nothing: no host compiler, source that is not host C++, probe switched off) goes into the hash —
-    // a module cached on a box where probing was impossible is not served where it works, and the reverse.
-    const std::string dir = libdir + "/models";
-    mkdir(dir.c_str(), 0755);
-    const bool large = src->nx > 4 || src->nu > 4;
-    ModelStructure ms;
-    if (large) {
-        char ptag[32];
-        std::snprintf(ptag, sizeof(ptag), "%016llx", hsh);
-        ms = probe_model_structure_cached(src, dir, ptag, hints);
-        mix(ms.found ? "probed" : "dense", 6);
-        if (ms.found) {
-            mix(ms.fxc.data(), ms.fxc.size() * 8); mix(ms.fuc.data(), ms.fuc.size() * 8);
-            if (!ms.jac_var.empty()) mix(ms.jac_var.data(), ms.jac_var.size() * sizeof(int));
-            if (!ms.hess_idx.empty()) mix(ms.hess_idx.data(), ms.hess_idx.size() * sizeof(int));
-        }
-    }
-    char tag[32];
-    std::snprintf(tag, sizeof(tag), "%016llx", hsh);
-    const std::string uname = std::string(src->name) + "_c" + tag;
-    // source and log are written under process-unique names: ranks compiling the same model at the same time must not truncate
-    // each other's input under a running hipcc (the module itself is moved into place atomically)
-    const std::string pid = std::to_string((long)getpid());
-    const std::string so = dir + "/libilqr_model_" + uname + ".so", hip = dir + "/model_" + uname + "." + pid + ".hip",
-                      log = dir + "/model_" + uname + "." + pid + ".log";
-    if (uname.size() + 1 > name_len || so.size() + 1 > path_len) return fail(ILQR_ERR_INVALID, "output buffers too small");
-    struct stat st;
-    if (stat(so.c_str(), &st) != 0) {
-        FILE* f = std::fopen(hip.c_str(), "w");
-        if (!f) return fail(ILQR_ERR_MODEL, "cannot write " + hip);
-        const bool cs = src->nc_stage > 0, ct = src->nc_term > 0;
-        std::fprintf(f, "// GENERATED by ilqr_compile_model — user callables wrapped for the kernels (ilqr_model_adapter.hpp)\n"
-                        "#include \"ilqr_model_adapter.hpp\"\nnamespace user_%s {\n%s\n}\n", tag, src->source);
-        std::fprintf(f, "struct Fns_%s {\n", tag);
-        const char* names[] = {"dynamics", "dynamics_jacobian_state", "dynamics_jacobian_action", "cost_stage", "cost_stage_gradient_state",
-                               "cost_stage_gradient_action", "cost_stage_hessian_state_state", "cost_stage_hessian_action_action",
-                               "cost_stage_hessian_action_state", "cost_terminal", "cost_terminal_gradient_state",
-                               "cost_terminal_hessian_state_state"};
-        for (const char* nm : names)
-            std::fprintf(f, "    ILQR_MODEL_FN void %s(double* o, const double* x, const double* u, const double* w) { user_%s::%s(o, x, u, w); }\n", nm, tag, nm);
-        const char* cnames[] = {"constraint_stage", "constraint_stage_jacobian_state", "constraint_stage_jacobian_action",
-                                "constraint_terminal", "constraint_terminal_jacobian_state"};
-        for (int i = 0; i < 5; ++i) {
-            const bool have = i < 3 ? cs : ct;
-            if (have) std::fprintf(f, "    ILQR_MODEL_FN void %s(double* o, const double* x, const double* u, const double* w) { user_%s::%s(o, x, u, w); }\n", cnames[i], tag, cnames[i]);
-            else std::fprintf(f, "    ILQR_MODEL_FN void %s(double*, const double*, const double*, const double*) {}\n", cnames[i]);
-        }
-        std::fprintf(f, "};\n");
-        // nx > 4 or nu > 4: the compact forms of the large path — with the constant / zero entries found by probing the callables
-        // on the host (probe_model_structure), dense when that is not possible
-        std::string tables;
-        if (large) {
-            if (ms.found) {
-                const int nn = src->nx, mm = src->nu, TNt = (nn + 15) / 16;
-                auto ilist = [](const std::vector<int>& v, size_t lo, size_t hi) { std::string o; for (size_t i = lo; i < hi; ++i) o += std::to_string(v[i]) + ","; if (hi == lo) o = "0"; return o; };
-                auto dlist = [](const std::vector<double>& v) { std::string o; char b[40]; for (double d : v) { std::snprintf(b, sizeof(b), "%.17g,", d); o += b; } return o; };
-                const int hs = (int)ms.hess_idx.size(), jv = (int)ms.jac_var.size();
-                std::fprintf(f, "// structure found on the host: %d of %d Jacobian entries state-dependent, %d + %d + %d of %d Hessian entries structurally non-zero\n"
-                                "struct Tables_%s {\n    static constexpr int TN = %d, NXX = %d, NUU = %d, NUX = %d, HS = %d, JV = %d;\n"
-                                "    struct Tab { int hess_idx[%d]; int tile_start[%d]; int jac_idx[%d]; double fxc[%d]; double fuc[%d]; };\n"
-                                "    static constexpr Tab tab = {{%s}, {%s}, {%s}, {%s}, {%s}};\n};\n",
-                             jv, nn * nn + nn * mm, ms.nxx, ms.nuu, ms.nux, nn * nn + mm * mm + mm * nn, tag, TNt, ms.nxx, ms.nuu, ms.nux, hs, jv,
-                             hs > 0 ? hs : 1, TNt * TNt + 1, jv > 0 ? jv : 1, nn * nn, nn * mm,
-                             ilist(ms.hess_idx, 0, ms.hess_idx.size()).c_str(), ilist(ms.tile_start, 0, ms.tile_start.size()).c_str(),
-                             ilist(ms.jac_var, 0, ms.jac_var.size()).c_str(), dlist(ms.fxc).c_str(), dlist(ms.fuc).c_str());
-                tables = std::string(", Tables_") + tag;
-            } else {
-                // dense tables: every Jacobian entry evaluated and stored per timestep, every Hessian entry streamed (correct, slow:
-                // kilobytes of per-thread arrays in the linearisation beyond nx = 16)
-                std::fprintf(f, "// no structure found (%s): dense tables\n", ms.note.c_str());
-            }
-        }
-        std::string words;       // more than 64 rows: the masks as word arrays (ilqr::IneqMask picks them up)
-        if (nwords > 1) {
-            auto wl = [](const std::vector<uint64_t>& v) { std::string o; char b[32]; for (uint64_t x : v) { std::snprintf(b, sizeof(b), "0x%llxull,", (unsigned long long)x); o += b; } return o; };
-            words = "    static constexpr int INEQ_WORDS = " + std::to_string(nwords) + ";\n    static constexpr unsigned long long INEQ_S_W[" +
-                    std::to_string(nwords) + "] = {" + wl(iw_s) + "}, INEQ_T_W[" + std::to_string(nwords) + "] = {" + wl(iw_t) + "};\n";
-        }
-        std::fprintf(f, "struct Model_%s : ilqr::%s<Fns_%s, %d, %d, %d, %d, %d, 0x%llxull, 0x%llxull%s> {\n"
-                        "    static constexpr const char* NAME = \"%s\";\n%s};\nILQR_DEFINE_MODEL(Model_%s)\n",
-                     uname.c_str(), large ? "AdaptedLargeModel" : "AdaptedModel", tag, src->nx, src->nu, src->nw, src->nc_stage, src->nc_term,
-                     (unsigned long long)iw_s[0], (unsigned long long)iw_t[0], tables.c_str(), uname.c_str(), words.c_str(), uname.c_str());
-        std::fclose(f);
-        // hipcc as a child process (no shell): same flags as the built-in models
-        const std::string tmp = so + ".tmp" + pid;
-        const std::string inc = "-I" + csrc, lflag = "-L" + libdir, rpath = "-Wl,-rpath," + libdir;
-        std::vector<const char*> argv = {hipcc.c_str(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mllvm",
-                                         "-amdgpu-mfma-vgpr-form", "-Wno-unused-parameter", inc.c_str(), hip.c_str(), "-o", tmp.c_str(),
-                                         lflag.c_str(), "-lilqr_hip", rpath.c_str(), nullptr};
-        posix_spawn_file_actions_t fa;
-        posix_spawn_file_actions_init(&fa);
-        posix_spawn_file_actions_addopen(&fa, 1, log.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
-        posix_spawn_file_actions_adddup2(&fa, 1, 2);
-        pid_t pid = 0;
-        extern char** environ;
-        const int sp = posix_spawn(&pid, hipcc.c_str(), &fa, nullptr, const_cast<char* const*>(argv.data()), environ);
-        posix_spawn_file_actions_destroy(&fa);
-        if (sp != 0) return fail(ILQR_ERR_MODEL, "cannot start " + hipcc + " (set ILQR_HIPCC)");
-        int status = 0;
-        if (waitpid(pid, &status, 0) < 0 || !WIFEXITED(status) || WEXITSTATUS(status) != 0) {
-            std::string msg = "hipcc failed for model '" + std::string(src->name) + "', see " + log;
-            if (FILE* lf = std::fopen(log.c_str(), "r")) {
-                char buf[1500];
-                const size_t nr = std::fread(buf, 1, sizeof(buf) - 1, lf);
-                buf[nr] = 0;
-                std::fclose(lf);
-                msg += ":\n" + std::string(buf);
-            }
-            return fail(ILQR_ERR_MODEL, msg);
-        }
-        if (std::rename(tmp.c_str(), so.c_str()) != 0) return fail(ILQR_ERR_MODEL, "cannot move the model module into place");
-        if (!std::getenv("ILQR_KEEP_MODEL_SOURCE")) std::remove(hip.c_str());      // (kept on request: the module's .hip next to its .so)
-        std::remove(log.c_str());
-    }
-    if (!dlopen(so.c_str(), RTLD_NOW | RTLD_GLOBAL)) return fail(ILQR_ERR_MODEL, std::string("dlopen failed: ") + dlerror());
-    if (!find_model(uname.c_str())) return fail(ILQR_ERR_MODEL, "the compiled module did not register '" + uname + "' (ABI mismatch?)");
-    std::snprintf(registered_name, name_len, "%s", uname.c_str());
-    std::snprintf(library_path, path_len, "%s", so.c_str());
-    return ILQR_OK;
-}
 const char* ilqr_model_name(int32_t i) {
     return (i >= 0 && i < (int)registry().size()) ? registry()[i]->name : nullptr;
 }
@@ -758,196 +395,6 @@ int ilqr_model_compact_sizes(const char* model, int32_t* jac_nvar, int32_t* hess
     if (jac_nvar) *jac_nvar = vt->jac_nvar;
     if (hess_nnz) *hess_nnz = vt->hess_nnz;
     return ILQR_OK;
-}
-
-// ---- Vectors of distinct per-step objects / time-varying dimensions, lowered onto the one-stage template (ilqr_hip.h).
-// What the reference does by indexing a Vector of objects with t (src/solver.jl:28-46, src/gradients.jl:1-21, src/rollout.jl:22-30)
-// becomes: one combined callable per category that branches on one-hot selector parameters, constraint kinds stacked row-wise,
-// every kind zero-padded to the largest dimensions of the horizon.
-int ilqr_plan_stages(const ilqr_stage_kinds* k, ilqr_stage_plan* plan, double* selectors, size_t selectors_len,
-                     int32_t* state_dims, int32_t* action_dims) {
-    if (!k || !plan) return fail(ILQR_ERR_INVALID, "null argument");
-    const int T = k->horizon, N = T - 1;
-    if (T < 2) return fail(ILQR_ERR_INVALID, "horizon must be >= 2");
-    if (k->n_dynamics < 1 || k->n_dynamics > ILQR_MAX_STAGE_KINDS || k->n_costs < 1 || k->n_costs > ILQR_MAX_STAGE_KINDS ||
-        k->n_constraints < 0 || k->n_constraints > ILQR_MAX_STAGE_KINDS)
-        return fail(ILQR_ERR_INVALID, "1 .. 16 dynamics kinds, 1 .. 16 stage-cost kinds, 0 .. 16 stage-constraint kinds");
-    if (!k->dynamics_nx || !k->dynamics_nu || !k->dynamics_nx_next || !k->dynamics_of_step || !k->cost_nx || !k->cost_nu || !k->cost_of_step ||
-        (k->n_constraints > 0 && (!k->constraint_nc || !k->constraint_nx || !k->constraint_nu || !k->constraint_ineq || !k->constraint_of_step)))
-        return fail(ILQR_ERR_INVALID, "null kind table");
-    if (k->num_parameter < 0 || k->nc_term < 0 || k->nc_term > ILQR_MAX_CONSTRAINT_ROWS) return fail(ILQR_ERR_INVALID, "num_parameter >= 0, 0 <= nc_term <= 256");
-    std::memset(plan, 0, sizeof(*plan));
-    // dimensions along the horizon (src/data/problem.jl:32-38) and the consistency the reference's broadcasts would enforce
-    std::vector<int> nt(T), mt(N);
-    for (int t = 0; t < N; ++t) {
-        const int d = k->dynamics_of_step[t], c = k->cost_of_step[t];
-        if (d < 0 || d >= k->n_dynamics || c < 0 || c >= k->n_costs) return fail(ILQR_ERR_INVALID, "kind index out of range at step " + std::to_string(t));
-        nt[t] = k->dynamics_nx[d]; mt[t] = k->dynamics_nu[d];
-        if (nt[t] < 1 || mt[t] < 1 || k->dynamics_nx_next[d] < 1) return fail(ILQR_ERR_INVALID, "dimensions must be >= 1");
-        if (t > 0 && k->dynamics_nx_next[k->dynamics_of_step[t - 1]] != nt[t])
-            return fail(ILQR_ERR_INVALID, "dynamics[" + std::to_string(t - 1) + "] does not produce the state of step " + std::to_string(t));
-        if (k->cost_nx[c] != nt[t] || k->cost_nu[c] != mt[t]) return fail(ILQR_ERR_INVALID, "cost[" + std::to_string(t) + "] dimensions are not its step's");
-        if (k->n_constraints > 0) {
-            const int q = k->constraint_of_step[t];
-            if (q < 0 || q >= k->n_constraints) return fail(ILQR_ERR_INVALID, "constraint kind index out of range at step " + std::to_string(t));
-            if (k->constraint_nc[q] < 0 || k->constraint_nc[q] > ILQR_MAX_CONSTRAINT_ROWS) return fail(ILQR_ERR_INVALID, "at most 256 rows per constraint kind");
-            if (k->constraint_nc[q] > 0 && (k->constraint_nx[q] != nt[t] || k->constraint_nu[q] != mt[t]))
-                return fail(ILQR_ERR_INVALID, "constraint[" + std::to_string(t) + "] dimensions are not its step's");
-        }
-    }
-    nt[N] = k->dynamics_nx_next[k->dynamics_of_step[N - 1]];
-    if (k->nx_term != nt[N]) return fail(ILQR_ERR_INVALID, "the terminal objects' num_state is not the last dynamics' num_next_state");
-    int n = 0, m = 0;
-    for (int t = 0; t < T; ++t) n = std::max(n, nt[t]);
-    for (int t = 0; t < N; ++t) m = std::max(m, mt[t]);
-    plan->nx = n; plan->nu = m; plan->nc_term = k->nc_term;
-    // stacked stage constraint: kind q owns rows [row0[q], row0[q] + nc_q)
-    int rows = 0;
-    for (int q = 0; q < k->n_constraints; ++q) {
-        plan->constraint_row0[q] = rows;
-        for (int i = 0; i < k->constraint_nc[q] && i < ILQR_MAX_CONSTRAINT_ROWS; ++i)
-            if ((k->constraint_ineq[4 * q + i / 64] >> (i % 64)) & 1ull) {
-                const int r = rows + i;
-                if (r < ILQR_MAX_CONSTRAINT_ROWS) plan->ineq_stage_words[r / 64] |= 1ull << (r % 64);
-            }
-        rows += k->constraint_nc[q];
-    }
-    if (rows > ILQR_MAX_CONSTRAINT_ROWS) return fail(ILQR_ERR_INVALID, "at most 256 stage constraint rows over all kinds");
-    plan->nc_stage = rows;
-    // selector blocks: one per category that really varies, in the order dynamics, cost, constraint, behind the user's parameters
-    int off = k->num_parameter;
-    plan->sel_dynamics = plan->sel_cost = plan->sel_constraint = -1;
-    const bool uniform = k->n_dynamics == 1 && k->n_costs == 1 && k->n_constraints <= 1;
-    if (!uniform) {
-        if (k->n_dynamics > 1) { plan->sel_dynamics = off; off += k->n_dynamics; }
-        if (k->n_costs > 1) { plan->sel_cost = off; off += k->n_costs; }
-        if (k->n_constraints > 1) { plan->sel_constraint = off; off += k->n_constraints; }
-    }
-    plan->nw = off; plan->n_selectors = off - k->num_parameter;
-    const int S = plan->n_selectors;
-    if (selectors) {
-        if (selectors_len < (size_t)T * (size_t)S) return fail(ILQR_ERR_INVALID, "selector buffer too small");
-        std::fill(selectors, selectors + (size_t)T * S, 0.0);
-        for (int t = 0; t < N; ++t) {
-            double* row = selectors + (size_t)t * S - k->num_parameter;          // indexed by parameter column
-            if (plan->sel_dynamics >= 0) row[plan->sel_dynamics + k->dynamics_of_step[t]] = 1.0;
-            if (plan->sel_cost >= 0) row[plan->sel_cost + k->cost_of_step[t]] = 1.0;
-            if (plan->sel_constraint >= 0) row[plan->sel_constraint + k->constraint_of_step[t]] = 1.0;
-        }
-    }
-    if (state_dims) for (int t = 0; t < T; ++t) state_dims[t] = nt[t];
-    if (action_dims) for (int t = 0; t < N; ++t) action_dims[t] = mt[t];
-    return ILQR_OK;
-}
-
-// The combined callables of the template, as C source around the kinds' own callables (which live in namespace kinds).
-static std::string compose_stage_source(const ilqr_stage_kinds* k, const ilqr_stage_plan& pl, const char* user_source) {
-    const int n = pl.nx, m = pl.nu;
-    std::string o = "namespace kinds {\n" + std::string(user_source) + "\n}\n";
-    const std::string sig = "(double* o, const double* x, const double* u, const double* w)";
-    auto S = [](int v) { return std::to_string(v); };
-    // `if (w[sel + k] > 0.5)` chain of a category; a category with one kind calls it unconditionally
-    auto branch = [&](int sel, int kinds, int kk) {
-        if (sel < 0 || kinds <= 1) return std::string("    {\n");
-        return std::string(kk == 0 ? "    if" : "    else if") + " (w[" + S(sel + kk) + "] > 0.5) {\n";
-    };
-    // call NAME into a (rows x cols, leading dimension ld_k) scratch and copy into o with leading dimension ld at row offset r0;
-    // direct when the layouts coincide
-    auto mat = [&](const std::string& name, int rows_k, int cols_k, int ld, int r0) {
-        if (rows_k == ld && r0 == 0) return "        kinds::" + name + "(o, x, u, w);\n";
-        if (rows_k * cols_k == 0) return std::string();
-        std::string c = "        double t[" + S(rows_k * cols_k) + "];\n        for (int i = 0; i < " + S(rows_k * cols_k) + "; ++i) t[i] = 0.0;\n";
-        c += "        kinds::" + name + "(t, x, u, w);\n";
-        c += "        for (int c = 0; c < " + S(cols_k) + "; ++c) for (int r = 0; r < " + S(rows_k) + "; ++r) o[c * " + S(ld) + " + " + S(r0) + " + r] = t[c * " + S(rows_k) + " + r];\n";
-        return c;
-    };
-    // ---- Dynamics (src/dynamics.jl:36-50): jacobian_state is num_next_state x num_state, jacobian_action num_next_state x num_action
-    const char* dsuf[3] = {"", "_jacobian_state", "_jacobian_action"};
-    for (int f = 0; f < 3; ++f) {
-        o += "ILQR_MODEL_FN void dynamics" + std::string(dsuf[f]) + sig + " {\n";
-        for (int q = 0; q < k->n_dynamics; ++q) {
-            const std::string nm = "dynamics_" + S(q) + dsuf[f];
-            o += branch(pl.sel_dynamics, k->n_dynamics, q);
-            if (f == 0) o += "        kinds::" + nm + "(o, x, u, w);\n";
-            else o += mat(nm, k->dynamics_nx_next[q], f == 1 ? k->dynamics_nx[q] : k->dynamics_nu[q], n, 0);
-            o += "    }\n";
-        }
-        o += "}\n";
-    }
-    // ---- stage Cost (src/costs.jl:48-84); padded actions cost u^2 / 2
-    const char* csuf[6] = {"", "_gradient_state", "_gradient_action", "_hessian_state_state", "_hessian_action_action", "_hessian_action_state"};
-    for (int f = 0; f < 6; ++f) {
-        o += "ILQR_MODEL_FN void cost_stage" + std::string(csuf[f]) + sig + " {\n";
-        for (int q = 0; q < k->n_costs; ++q) {
-            const std::string nm = "cost_stage_" + S(q) + csuf[f];
-            const int n0 = k->cost_nx[q], m0 = k->cost_nu[q];
-            o += branch(pl.sel_cost, k->n_costs, q);
-            if (f == 0) {
-                o += "        kinds::" + nm + "(o, x, u, w);\n";
-                if (m0 < m) {
-                    std::string sum;
-                    for (int j = m0; j < m; ++j) sum += (j > m0 ? " + " : "") + ("u[" + S(j) + "] * u[" + S(j) + "]");
-                    o += "        o[0] = o[0] + (" + sum + ") / 2.0;\n";
-                }
-            } else if (f == 1) o += "        kinds::" + nm + "(o, x, u, w);\n";
-            else if (f == 2) {
-                o += "        kinds::" + nm + "(o, x, u, w);\n";
-                for (int j = m0; j < m; ++j) o += "        o[" + S(j) + "] = u[" + S(j) + "];\n";
-            } else if (f == 3) o += mat(nm, n0, n0, n, 0);
-            else if (f == 4) {
-                o += mat(nm, m0, m0, m, 0);
-                for (int j = m0; j < m; ++j) o += "        o[" + S(j * m + j) + "] = 1.0;\n";
-            } else o += mat(nm, m0, n0, m, 0);
-            o += "    }\n";
-        }
-        o += "}\n";
-    }
-    // ---- terminal Cost: num_state = nx_term
-    o += "ILQR_MODEL_FN void cost_terminal" + sig + " { kinds::cost_terminal(o, x, u, w); }\n";
-    o += "ILQR_MODEL_FN void cost_terminal_gradient_state" + sig + " { kinds::cost_terminal_gradient_state(o, x, u, w); }\n";
-    o += "ILQR_MODEL_FN void cost_terminal_hessian_state_state" + sig + " {\n    {\n" + mat("cost_terminal_hessian_state_state", k->nx_term, k->nx_term, n, 0) + "    }\n}\n";
-    // ---- stage Constraint (src/constraints.jl:66-87): kinds stacked, kind q at rows row0[q] ..
-    if (pl.nc_stage > 0) {
-        const char* ksuf[3] = {"", "_jacobian_state", "_jacobian_action"};
-        for (int f = 0; f < 3; ++f) {
-            o += "ILQR_MODEL_FN void constraint_stage" + std::string(ksuf[f]) + sig + " {\n";
-            bool first = true;
-            for (int q = 0; q < k->n_constraints; ++q) {
-                if (k->constraint_nc[q] == 0) continue;
-                const std::string nm = "constraint_stage_" + S(q) + ksuf[f];
-                if (pl.sel_constraint < 0) o += "    {\n";
-                else o += std::string(first ? "    if" : "    else if") + " (w[" + S(pl.sel_constraint + q) + "] > 0.5) {\n";
-                first = false;
-                if (f == 0) o += "        kinds::" + nm + "(o + " + S(pl.constraint_row0[q]) + ", x, u, w);\n";
-                else o += mat(nm, k->constraint_nc[q], f == 1 ? k->constraint_nx[q] : k->constraint_nu[q], pl.nc_stage, pl.constraint_row0[q]);
-                o += "    }\n";
-            }
-            o += "}\n";
-        }
-    }
-    // ---- terminal Constraint: nc_term x nx_term, column-major with leading dimension nc_term — the template's nc_term x nx has the same
-    if (k->nc_term > 0) {
-        o += "ILQR_MODEL_FN void constraint_terminal" + sig + " { kinds::constraint_terminal(o, x, u, w); }\n";
-        o += "ILQR_MODEL_FN void constraint_terminal_jacobian_state" + sig + " { kinds::constraint_terminal_jacobian_state(o, x, u, w); }\n";
-    }
-    return o;
-}
-
-int ilqr_compile_model_stages(const char* name, const ilqr_stage_kinds* kinds, const char* source, ilqr_stage_plan* plan,
-                              double* selectors, size_t selectors_len, int32_t* state_dims, int32_t* action_dims,
-                              char* registered_name, size_t name_len, char* library_path, size_t path_len) {
-    if (!name || !kinds || !source || !plan) return fail(ILQR_ERR_INVALID, "null argument");
-    const int rc = ilqr_plan_stages(kinds, plan, selectors, selectors_len, state_dims, action_dims);
-    if (rc != ILQR_OK) return rc;
-    const std::string combined = compose_stage_source(kinds, *plan, source);
-    ilqr_model_source ms;
-    ms.name = name; ms.nx = plan->nx; ms.nu = plan->nu; ms.nw = plan->nw; ms.nc_stage = plan->nc_stage; ms.nc_term = plan->nc_term;
-    ms.ineq_stage = plan->ineq_stage_words[0]; ms.ineq_term = kinds->ineq_term[0]; ms.source = combined.c_str(); ms.flags = 0;
-    ProbeHints hints;
-    hints.sel[0] = plan->sel_dynamics; hints.kinds[0] = plan->sel_dynamics >= 0 ? kinds->n_dynamics : 0;
-    hints.sel[1] = plan->sel_cost; hints.kinds[1] = plan->sel_cost >= 0 ? kinds->n_costs : 0;
-    hints.sel[2] = plan->sel_constraint; hints.kinds[2] = plan->sel_constraint >= 0 ? kinds->n_constraints : 0;
-    return compile_model_impl(&ms, plan->ineq_stage_words, kinds->ineq_term, registered_name, name_len, library_path, path_len, hints);
 }
 
 int ilqr_create(const ilqr_problem_desc* d, ilqr_handle** out) {
