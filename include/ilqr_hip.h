@@ -130,6 +130,30 @@ int ilqr_initialize_rollout_device(ilqr_handle* h, const double* d_x1, const dou
  * src/solver.jl:56-66 — without a host-to-device copy. Asynchronous. */
 int ilqr_initialize_rollout_resident(ilqr_handle* h);
 
+/* The same from the best of `candidates` action sequences per instance. Every candidate s of instance b is rolled out open-loop
+ * from x1[b] under the handle's parameters (selector columns included), x = rollout(dynamics, x1[b], u[b][s]), src/rollout.jl:33-42,
+ * and scored on the device: cost = the plain objective Σ cost (src/costs.jl:48-55, summed in timestep order; not the
+ * augmented-Lagrangian merit), max_violation = constraint_violation over its trajectory (src/data/constraints.jl:23-39; 0 on a
+ * handle created unconstrained), first_nonfinite = −1 or the first 0-based t at which a component of x_t is not finite (as in
+ * ilqr_rollout_policy). score = cost when violation_weight == 0, else cost + violation_weight · max_violation. A candidate is
+ * eligible when its score is finite and its first_nonfinite is −1; chosen[b] = the eligible candidate with the lowest score, ties
+ * to the lowest index, or −1 when none is eligible — candidate 0 is installed then, so the handle's state is always defined.
+ * Afterwards the handle is in exactly the state ilqr_initialize_rollout(h, x1, u[:, chosen]) leaves it in (x̄, ū,
+ * states_eq_nominal, the resident inputs: ilqr_initialize_rollout_resident replays the winners); policy, duals, scalars, trace
+ * and timing are untouched. Refused (ILQR_ERR_INVALID) without touching the GPU: candidates < 1, null x1 or u, a negative or
+ * non-finite violation_weight. Host form: stages through device buffers the handle owns and reuses; on a sharded handle every
+ * instance's candidates go to the device that owns the instance. Device form: every pointer a device pointer on the handle's
+ * device, asynchronous on the handle's stream; refused on a sharded handle. */
+int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, double violation_weight,
+                                       const double* x1,            /* [B][nx] */
+                                       const double* u,             /* [B][S][T-1][nu] */
+                                       int32_t* chosen,             /* NULL, or [B] */
+                                       double* cost,                /* NULL, or [B][S] */
+                                       double* max_violation,       /* NULL, or [B][S] */
+                                       int32_t* first_nonfinite);   /* NULL, or [B][S] */
+int ilqr_initialize_rollout_candidates_device(ilqr_handle* h, int32_t candidates, double violation_weight, const double* d_x1, const double* d_u,
+                                              int32_t* d_chosen, double* d_cost, double* d_max_violation, int32_t* d_first_nonfinite);
+
 /* solve!(solver) — src/solve.jl:137-143. Asynchronous: enqueues the whole
  * AL/iLQR solve of every instance on the handle's stream. */
 int ilqr_solve(ilqr_handle* h);

@@ -172,6 +172,34 @@ class Solver:
         handle that spans several devices, where device pointers of one device make no sense)."""
         _ffi.check(_ffi.lib().ilqr_initialize_rollout_resident(self._h))
 
+    def initialize_rollout_candidates_(self, x1, u, violation_weight=0.0):
+        """initialize_rollout_ from the best of S candidate action sequences per instance (ilqr_initialize_rollout_candidates):
+        x1 [B, nx], u [B, S, T-1, nu]. Every candidate is rolled out and scored on the device, score = cost (+ violation_weight ·
+        max_violation); the eligible candidate (finite score, no non-finite state) with the lowest score, ties to the lowest
+        index, is installed exactly as initialize_rollout_(x1, u[:, chosen]) would install it. Returns a dict with chosen [B]
+        (−1: nobody eligible, candidate 0 installed), cost, max_violation and first_nonfinite [B, S]."""
+        x1 = np.ascontiguousarray(x1, dtype=np.float64).reshape(self.B, self.nx)
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        per = (self.T - 1) * self.nu
+        if u.ndim < 2 or u.shape[0] != self.B or u.size == 0 or u.size % (self.B * per) != 0:
+            raise ValueError("u must have shape [B, S, T-1, nu]")
+        S = u.size // (self.B * per)
+        u = u.reshape(self.B, S, self.T - 1, self.nu)
+        i32 = C.POINTER(C.c_int32)
+        out = dict(chosen=np.empty(self.B, dtype=np.int32), cost=np.empty((self.B, S)), max_violation=np.empty((self.B, S)),
+                   first_nonfinite=np.empty((self.B, S), dtype=np.int32))
+        _ffi.check(_ffi.lib().ilqr_initialize_rollout_candidates(self._h, S, float(violation_weight), _p(x1), _p(u), out["chosen"].ctypes.data_as(i32),
+                                                                 _p(out["cost"]), _p(out["max_violation"]), out["first_nonfinite"].ctypes.data_as(i32)))
+        return out
+
+    def initialize_rollout_candidates_device_(self, candidates, d_x1_ptr, d_u_ptr, violation_weight=0.0, d_chosen_ptr=None, d_cost_ptr=None,
+                                              d_max_violation_ptr=None, d_first_nonfinite_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not wanted); asynchronous on the handle's stream."""
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_initialize_rollout_candidates_device(self._h, int(candidates), float(violation_weight), vp(d_x1_ptr), vp(d_u_ptr),
+                                                                        vp(d_chosen_ptr), vp(d_cost_ptr), vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr)))
+
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""
         w = np.ascontiguousarray(w, dtype=np.float64).reshape(self.B, self.T, self.num_user_parameter)

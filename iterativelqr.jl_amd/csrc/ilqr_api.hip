@@ -135,6 +135,9 @@ struct ilqr_handle {
     // device staging of its host form — x1, w, cost, max_violation, first_nonfinite, x, u — which grows on demand and is reused
     bool has_policy = false;
     struct Stage { void* p = nullptr; size_t cap = 0; } pol[7];
+    // ilqr_initialize_rollout_candidates: the device staging of the candidates' u (host form) and the score buffers the caller
+    // did not ask for — u, cost, max_violation, first_nonfinite, chosen — grown on demand and reused
+    Stage cand[5];
 };
 
 namespace {
@@ -500,6 +503,7 @@ int ilqr_destroy(ilqr_handle* h) {
     if (h->cu_slots) hipFree(h->cu_slots);
     if (h->d_u) hipFree(h->d_u);
     for (auto& st : h->pol) if (st.p) hipFree(st.p);
+    for (auto& st : h->cand) if (st.p) hipFree(st.p);
     if (h->trace) hipFree(h->trace);
     if (h->qv) hipFree(h->qv);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -966,6 +970,94 @@ int ilqr_rollout_policy(ilqr_handle* h, int32_t samples, double step_size, const
     if (rc != ILQR_OK) return rc;
     void* host[7] = {nullptr, nullptr, cost, max_violation, first_nonfinite, x, u};
     for (int i = 2; i < 7; ++i)
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ILQR_OK;
+}
+
+// ---- scoring and selection of candidate initial guesses (ilqr_device_candidates.hpp), then the existing init_rollout on the winners
+// everything that can be refused without touching the GPU, before the handle is looked at
+static int candidates_check(const ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u, const char* who) {
+    const std::string me(who);
+    if (candidates < 1) return fail(ILQR_ERR_INVALID, me + ": candidates must be >= 1");
+    if (!x1) return fail(ILQR_ERR_INVALID, me + ": null x1");
+    if (!u) return fail(ILQR_ERR_INVALID, me + ": null u");
+    if (!(violation_weight >= 0.0) || !std::isfinite(violation_weight)) return fail(ILQR_ERR_INVALID, me + ": violation_weight must be finite and >= 0");
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    return ILQR_OK;
+}
+
+static int grow(ilqr_handle* h, ilqr_handle::Stage& st, size_t bytes) {
+    if (bytes <= st.cap) return ILQR_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (st.p) { HIP_TRY(hipFree(st.p)); st.p = nullptr; st.cap = 0; }
+    HIP_TRY(hipMalloc(&st.p, bytes));
+    st.cap = bytes;
+    return ILQR_OK;
+}
+
+// every pointer a device pointer on h's device; x1 may be h->d_x1 itself. Null outputs are replaced by the handle's own buffers.
+static int candidates_launch(ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u, int32_t* chosen,
+                             double* cost, double* max_violation, int32_t* first_nonfinite) {
+    if (!h->vt->launch_candidates) return fail(ILQR_ERR_MODEL, "this model module has no candidate scoring kernel");
+    const size_t BS = (size_t)h->B * (size_t)candidates;
+    if (!cost) { const int rc = grow(h, h->cand[1], BS * 8); if (rc != ILQR_OK) return rc; cost = (double*)h->cand[1].p; }
+    if (!max_violation) { const int rc = grow(h, h->cand[2], BS * 8); if (rc != ILQR_OK) return rc; max_violation = (double*)h->cand[2].p; }
+    if (!first_nonfinite) { const int rc = grow(h, h->cand[3], BS * 4); if (rc != ILQR_OK) return rc; first_nonfinite = (int32_t*)h->cand[3].p; }
+    ilqr::CandArgs a;
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = candidates; a.constrained = h->constrained;
+    a.waves = (candidates + 63) / 64 > 4 ? 4 : (candidates + 63) / 64;
+    a.weight = violation_weight; a.x1 = x1; a.u = u; a.cost = cost; a.viol = max_violation; a.nonfinite = first_nonfinite; a.chosen = chosen;
+    a.r_x1 = h->d_x1; a.r_u = h->d_u;
+    if (h->vt->launch_candidates(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "candidate scoring launch failed");
+    return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);       // the code that defines the installed state
+}
+
+static int resident_inputs(ilqr_handle* h) {
+    const size_t bx = (size_t)h->B * h->vt->nx * 8, bu = (size_t)h->B * (h->L.T - 1) * h->vt->nu * 8;
+    if (!h->d_x1) HIP_TRY(hipMalloc((void**)&h->d_x1, bx));
+    if (!h->d_u) HIP_TRY(hipMalloc((void**)&h->d_u, bu));
+    return ILQR_OK;
+}
+
+int ilqr_initialize_rollout_candidates_device(ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u,
+                                              int32_t* chosen, double* cost, double* max_violation, int32_t* first_nonfinite) {
+    int rc = candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates_device");
+    if (rc != ILQR_OK) return rc;
+    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_initialize_rollout_candidates (host pointers) on a sharded handle");
+    HIP_TRY(hipSetDevice(h->device));
+    rc = resident_inputs(h);
+    if (rc != ILQR_OK) return rc;
+    return candidates_launch(h, candidates, violation_weight, x1, u, chosen, cost, max_violation, first_nonfinite);
+}
+
+int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u,
+                                       int32_t* chosen, double* cost, double* max_violation, int32_t* first_nonfinite) {
+    int rc = candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates");
+    if (rc != ILQR_OK) return rc;
+    const size_t S = (size_t)candidates, N = (size_t)h->L.T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        const size_t o = lo * S;
+        return ilqr_initialize_rollout_candidates(s, candidates, violation_weight, x1 + lo * n, u + o * N * m, chosen ? chosen + lo : nullptr,
+                                                  cost ? cost + o : nullptr, max_violation ? max_violation + o : nullptr,
+                                                  first_nonfinite ? first_nonfinite + o : nullptr); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    rc = resident_inputs(h);
+    if (rc != ILQR_OK) return rc;
+    const size_t B = (size_t)h->B, BS = B * S;
+    const size_t bytes[5] = {BS * N * m * 8, cost ? BS * 8 : 0, max_violation ? BS * 8 : 0, first_nonfinite ? BS * 4 : 0, chosen ? B * 4 : 0};
+    void* d[5];
+    for (int i = 0; i < 5; ++i) {
+        rc = grow(h, h->cand[i], bytes[i]);
+        if (rc != ILQR_OK) return rc;
+        d[i] = bytes[i] ? h->cand[i].p : nullptr;
+    }
+    HIP_TRY(hipMemcpyAsync(h->d_x1, x1, B * n * 8, hipMemcpyHostToDevice, h->stream));
+    if (bytes[0]) HIP_TRY(hipMemcpyAsync(d[0], u, bytes[0], hipMemcpyHostToDevice, h->stream));
+    rc = candidates_launch(h, candidates, violation_weight, h->d_x1, bytes[0] ? (const double*)d[0] : h->d_u, (int32_t*)d[4], (double*)d[1], (double*)d[2], (int32_t*)d[3]);
+    if (rc != ILQR_OK) return rc;
+    void* host[5] = {nullptr, cost, max_violation, first_nonfinite, chosen};
+    for (int i = 1; i < 5; ++i)
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;

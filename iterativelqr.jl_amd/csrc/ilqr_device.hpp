@@ -2322,10 +2322,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 }  // namespace ilqr
 #include "ilqr_device_packed.hpp"
 #include "ilqr_device_policy.hpp"
+#include "ilqr_device_candidates.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 12   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 13   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2346,6 +2347,9 @@ extern "C" struct ilqr_model_vtable {
     int packed1_lds_bytes, packed2_lds_bytes;
     // closed-loop rollouts of the handle's policy from the caller's initial states (ilqr_device_policy.hpp): reads the workspace only
     int (*launch_policy_rollout)(const ilqr::PolicyArgs* a, void* stream);
+    // scoring of candidate initial guesses, then per instance the argmin and the copy of the winner into the resident inputs
+    // (ilqr_device_candidates.hpp)
+    int (*launch_candidates)(const ilqr::CandArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2405,7 +2409,8 @@ struct ModelModule {
                                              M::NAME, M::NX, M::NU, M::NW, M::NCS, M::NCT, M::INEQ_S, M::INEQ_T,
                                              &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
-                                             packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>};
+                                             packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
+                                             &launch_candidates<M>};
         return &vt;
     }
 };

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 const LIB = Ref{String}(joinpath(@__DIR__, "..", "lib", "libilqr_hip.so"))
@@ -120,6 +120,22 @@ end
 function initialize_rollout!(s::Solver, x1::Matrix{Float64}, u::Array{Float64,3})
     @assert size(x1) == (s.nx, s.B) && size(u) == (s.nu, s.T - 1, s.B)
     check(ccall((:ilqr_initialize_rollout, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.handle, x1, u))
+end
+
+# initialize_rollout! from the best of S candidate action sequences per instance (ilqr_initialize_rollout_candidates):
+# u :: (nu, T-1, S, B). Every candidate is rolled out and scored on the device, score = cost (+ violation_weight · max_violation);
+# the eligible candidate with the lowest score (ties: lowest index) is installed as initialize_rollout! would install it.
+# Returns (chosen, cost, max_violation, first_nonfinite): chosen is 1-based per instance, 0 when no candidate was eligible
+# (candidate 1 is installed then); the others are S×B.
+function initialize_rollout_candidates!(s::Solver, x1::Matrix{Float64}, u::Array{Float64,4}; violation_weight::Float64 = 0.0)
+    @assert size(x1) == (s.nx, s.B) && size(u, 1) == s.nu && size(u, 2) == s.T - 1 && size(u, 4) == s.B
+    S = size(u, 3)
+    chosen = Vector{Int32}(undef, s.B)
+    cost = Array{Float64,2}(undef, S, s.B); viol = Array{Float64,2}(undef, S, s.B); nonfinite = Array{Int32,2}(undef, S, s.B)
+    check(ccall((:ilqr_initialize_rollout_candidates, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                s.handle, Int32(S), violation_weight, x1, u, chosen, cost, viol, nonfinite))
+    return chosen .+ Int32(1), cost, viol, nonfinite
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
