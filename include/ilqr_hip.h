@@ -154,6 +154,30 @@ int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, doubl
 int ilqr_initialize_rollout_candidates_device(ilqr_handle* h, int32_t candidates, double violation_weight, const double* d_x1, const double* d_u,
                                               int32_t* d_chosen, double* d_cost, double* d_max_violation, int32_t* d_first_nonfinite);
 
+/* Receding-horizon shift of a solved handle by k = `steps` control periods, on the device (N = T − 1; x̄, ū, K, θ as the handle
+ * holds them when the call is made). Start state: x1'[b] = x1[b] (the measured state) if given, else x̄_k[b]. Parameters (models
+ * with user parameters only): θ'_t = θ_{t+k} for t + k <= T−1; the remaining k rows are w_tail[b][t − (T−k)] if given, else
+ * θ_{T−1}. Actions, feedback == 0: u'_t = ū_{t+k} for t < N−k (pure copies), then ū_{N−1} (ILQR_SHIFT_TAIL_HOLD) or 0
+ * (ILQR_SHIFT_TAIL_ZERO). feedback != 0: the shifted policy run closed-loop from x1' under θ' over the head,
+ * u'_t = ū_{t+k} + K_{t+k} (x'_t − x̄_{t+k}), x'_{t+1} = f(x'_t, u'_t, θ'_t), x'_0 = x1' (src/rollout.jl:24-29 with α = 0, formed as
+ * (ū + K x') − K x̄), t < N−k; the tail as above, on ū without feedback — no gain exists beyond the horizon. (x1', u') go to the
+ * handle's resident inputs and ilqr_initialize_rollout_device runs on them: afterwards the handle is in exactly the state
+ * ilqr_set_parameters(h, θ') + ilqr_initialize_rollout(h, x1', u') leave it in, and ilqr_initialize_rollout_resident replays it.
+ * K, k, P, p, duals, penalties, the named scalars, trace and timing are untouched (the policy is stale afterwards, as after every
+ * initialiser). steps == 0 is allowed: with feedback and an x1 it re-anchors the nominal trajectory at a measured state.
+ * Refused (ILQR_ERR_INVALID) without touching the GPU: a null handle, steps < 0 or > T−1, an unknown tail, w_tail on a model
+ * without user parameters or with steps == 0, steps > 0 on a handle with stage selectors (a lowered problem's structure belongs to
+ * horizon positions), feedback without a policy (the rule of ilqr_rollout_policy). Host form: x1 and w_tail are staged through
+ * device buffers the handle owns and reuses; works on a sharded handle; synchronous. Device form: device pointers on the handle's
+ * device, asynchronous on the handle's stream; refused on a sharded handle. */
+#define ILQR_SHIFT_TAIL_HOLD 0
+#define ILQR_SHIFT_TAIL_ZERO 1
+int ilqr_shift_horizon(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback,
+                       const double* x1,      /* NULL, or [B][nx]: the measured states */
+                       const double* w_tail); /* NULL, or [B][steps][nw_user] */
+int ilqr_shift_horizon_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback,
+                              const double* d_x1, const double* d_w_tail);
+
 /* solve!(solver) — src/solve.jl:137-143. Asynchronous: enqueues the whole
  * AL/iLQR solve of every instance on the handle's stream. */
 int ilqr_solve(ilqr_handle* h);

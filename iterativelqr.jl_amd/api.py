@@ -200,6 +200,41 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_initialize_rollout_candidates_device(self._h, int(candidates), float(violation_weight), vp(d_x1_ptr), vp(d_u_ptr),
                                                                         vp(d_chosen_ptr), vp(d_cost_ptr), vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr)))
 
+    _TAILS = {"hold": 0, "zero": 1}
+
+    def _shift_arguments(self, steps, tail):
+        steps = int(steps)
+        if not 0 <= steps <= self.T - 1:
+            raise ValueError("steps must lie in 0 .. T-1")
+        if tail not in self._TAILS:
+            raise ValueError('tail must be "hold" or "zero"')
+        return steps, self._TAILS[tail]
+
+    def shift_horizon_(self, steps=1, x1=None, feedback=False, tail="hold", w_tail=None):
+        """Receding-horizon shift on the device (ilqr_shift_horizon): the solved trajectory moves forward by `steps` control periods
+        and is installed as initialize_rollout_ would install it. x1 [B, nx]: the measured states (None: x̄_steps). The actions are
+        ū_{t+steps}, then the last action held (tail="hold") or 0 ("zero"); with feedback=True the head is the shifted policy run
+        closed-loop from x1, u'_t = ū_{t+steps} + K_{t+steps} (x'_t − x̄_{t+steps}). The parameters move with the horizon; their last
+        `steps` rows are w_tail [B, steps, num_parameter] or, without it, the last row held. The policy, duals and scalars stay."""
+        steps, tail = self._shift_arguments(steps, tail)
+        if x1 is not None:
+            x1 = np.ascontiguousarray(x1, dtype=np.float64)
+            if x1.shape != (self.B, self.nx):
+                raise ValueError("x1 must have shape [B, nx]")
+        if w_tail is not None:
+            w_tail = np.ascontiguousarray(w_tail, dtype=np.float64)
+            if self.num_user_parameter > 0 and steps > 0 and w_tail.shape != (self.B, steps, self.num_user_parameter):
+                raise ValueError("w_tail must have shape [B, steps, num_parameter]")
+        _ffi.check(_ffi.lib().ilqr_shift_horizon(self._h, steps, tail, 1 if feedback else 0, _p(x1) if x1 is not None else None,
+                                                 _p(w_tail) if w_tail is not None else None))
+
+    def shift_horizon_device_(self, steps=1, d_x1_ptr=None, feedback=False, tail="hold", d_w_tail_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not given); asynchronous on the handle's stream."""
+        steps, tail = self._shift_arguments(steps, tail)
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_shift_horizon_device(self._h, steps, tail, 1 if feedback else 0, vp(d_x1_ptr), vp(d_w_tail_ptr)))
+
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""
         w = np.ascontiguousarray(w, dtype=np.float64).reshape(self.B, self.T, self.num_user_parameter)

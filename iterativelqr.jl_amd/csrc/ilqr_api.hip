@@ -138,6 +138,9 @@ struct ilqr_handle {
     // ilqr_initialize_rollout_candidates: the device staging of the candidates' u (host form) and the score buffers the caller
     // did not ask for — u, cost, max_violation, first_nonfinite, chosen — grown on demand and reused
     Stage cand[5];
+    // ilqr_shift_horizon: the device staging of x1 and w_tail (host form) and of the shifted parameters θ' of the whole batch,
+    // which are read out of the workspace before a second launch writes them back — grown on demand and reused
+    Stage shift[3];
 };
 
 namespace {
@@ -504,6 +507,7 @@ int ilqr_destroy(ilqr_handle* h) {
     if (h->d_u) hipFree(h->d_u);
     for (auto& st : h->pol) if (st.p) hipFree(st.p);
     for (auto& st : h->cand) if (st.p) hipFree(st.p);
+    for (auto& st : h->shift) if (st.p) hipFree(st.p);
     if (h->trace) hipFree(h->trace);
     if (h->qv) hipFree(h->qv);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1060,6 +1064,73 @@ int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, doubl
     for (int i = 1; i < 5; ++i)
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
+    return ILQR_OK;
+}
+
+// ---- receding-horizon shift (ilqr_device_shift.hpp), then the existing init_rollout on the shifted inputs
+// everything that can be refused without touching the GPU
+static int shift_check(const ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* w_tail, const char* who) {
+    const std::string me(who);
+    if (steps < 0) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 0 .. T-1");
+    if (tail != ILQR_SHIFT_TAIL_HOLD && tail != ILQR_SHIFT_TAIL_ZERO) return fail(ILQR_ERR_INVALID, me + ": unknown tail mode");
+    if (w_tail && steps == 0) return fail(ILQR_ERR_INVALID, me + ": w_tail given with steps == 0: no parameter row enters the horizon");
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (steps > h->L.T - 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 0 .. T-1");
+    if (w_tail && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_tail given, but this model has no parameters (num_parameter == 0)");
+    if (steps > 0 && h->n_sel > 0)
+        return fail(ILQR_ERR_INVALID, me + ": the handle has stage selectors attached: the structure of a lowered problem belongs to horizon positions and cannot be shifted");
+    if (feedback) {
+        bool pol = h->has_policy;
+        if (!h->shards.empty()) { pol = true; for (const ilqr_handle* s : h->shards) pol = pol && s->has_policy; }
+        if (!pol) return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
+    }
+    return ILQR_OK;
+}
+
+// x1, w_tail: null or device pointers on h's device
+static int shift_launch(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
+    if (!h->vt->launch_shift) return fail(ILQR_ERR_MODEL, "this model module has no horizon shift kernel");
+    int rc = resident_inputs(h);
+    if (rc != ILQR_OK) return rc;
+    ilqr::ShiftArgs a;
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.tail = tail; a.feedback = feedback ? 1 : 0; a.phase = 0;
+    a.x1 = x1; a.w_tail = w_tail; a.w_stage = nullptr; a.r_x1 = h->d_x1; a.r_u = h->d_u;
+    if (steps > 0 && h->L.nw > 0) {            // (no selectors here: every parameter column is the user's)
+        rc = grow(h, h->shift[2], (size_t)h->B * h->L.T * h->L.nw * 8);
+        if (rc != ILQR_OK) return rc;
+        a.w_stage = (double*)h->shift[2].p;
+    }
+    if (h->vt->launch_shift(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "horizon shift launch failed");
+    return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);       // the code that defines the installed state
+}
+
+int ilqr_shift_horizon_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
+    const int rc = shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon_device");
+    if (rc != ILQR_OK) return rc;
+    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_shift_horizon (host pointers) on a sharded handle");
+    HIP_TRY(hipSetDevice(h->device));
+    return shift_launch(h, steps, tail, feedback, x1, w_tail);
+}
+
+int ilqr_shift_horizon(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
+    int rc = shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon");
+    if (rc != ILQR_OK) return rc;
+    const size_t n = (size_t)h->L.nx, kw = (size_t)steps * (size_t)(h->L.nw - h->n_sel);
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_shift_horizon(s, steps, tail, feedback, x1 ? x1 + lo * n : nullptr, w_tail ? w_tail + lo * kw : nullptr); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t bytes[2] = {x1 ? (size_t)h->B * n * 8 : 0, w_tail ? (size_t)h->B * kw * 8 : 0};
+    const double* host[2] = {x1, w_tail};
+    const double* d[2];
+    for (int i = 0; i < 2; ++i) {
+        rc = grow(h, h->shift[i], bytes[i]);
+        if (rc != ILQR_OK) return rc;
+        d[i] = bytes[i] ? (const double*)h->shift[i].p : nullptr;
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(h->shift[i].p, host[i], bytes[i], hipMemcpyHostToDevice, h->stream));
+    }
+    rc = shift_launch(h, steps, tail, feedback, d[0], d[1]);
+    if (rc != ILQR_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller
     return ILQR_OK;
 }
 

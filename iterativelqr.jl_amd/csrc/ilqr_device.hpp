@@ -2323,10 +2323,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_packed.hpp"
 #include "ilqr_device_policy.hpp"
 #include "ilqr_device_candidates.hpp"
+#include "ilqr_device_shift.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 13   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 14   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2350,6 +2351,8 @@ extern "C" struct ilqr_model_vtable {
     // scoring of candidate initial guesses, then per instance the argmin and the copy of the winner into the resident inputs
     // (ilqr_device_candidates.hpp)
     int (*launch_candidates)(const ilqr::CandArgs* a, void* stream);
+    // receding-horizon shift of the solved trajectory (and of θ) into the resident inputs (ilqr_device_shift.hpp)
+    int (*launch_shift)(const ilqr::ShiftArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2410,7 +2413,7 @@ struct ModelModule {
                                              &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
-                                             &launch_candidates<M>};
+                                             &launch_candidates<M>, &launch_shift<M>};
         return &vt;
     }
 };

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, shift_horizon!,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 const LIB = Ref{String}(joinpath(@__DIR__, "..", "lib", "libilqr_hip.so"))
@@ -136,6 +136,22 @@ function initialize_rollout_candidates!(s::Solver, x1::Matrix{Float64}, u::Array
                 (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
                 s.handle, Int32(S), violation_weight, x1, u, chosen, cost, viol, nonfinite))
     return chosen .+ Int32(1), cost, viol, nonfinite
+end
+
+# Receding-horizon shift on the device (ilqr_shift_horizon): the solved trajectory moves forward by `steps` control periods and is
+# installed as initialize_rollout! would install it. x1 :: (nx, B), the measured states (nothing: x̄ at step `steps`); tail = :hold
+# keeps the last action over the new steps, :zero writes 0; feedback = true runs the shifted policy closed-loop from x1 over the
+# head of the horizon. The parameters move with the horizon: their last `steps` columns are w_tail :: (nw, steps, B) or the last
+# column held. Policy, duals and scalars stay.
+function shift_horizon!(s::Solver; steps::Integer = 1, x1::Union{Nothing,Matrix{Float64}} = nothing, feedback::Bool = false,
+                        tail::Symbol = :hold, w_tail::Union{Nothing,Array{Float64,3}} = nothing)
+    @assert 0 <= steps <= s.T - 1 && (tail === :hold || tail === :zero)
+    @assert x1 === nothing || size(x1) == (s.nx, s.B)
+    @assert w_tail === nothing || (size(w_tail, 2) == steps && size(w_tail, 3) == s.B)
+    nul = Ptr{Float64}(C_NULL)
+    check(ccall((:ilqr_shift_horizon, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                s.handle, Int32(steps), Int32(tail === :hold ? 0 : 1), Int32(feedback ? 1 : 0), x1 === nothing ? nul : x1,
+                w_tail === nothing ? nul : w_tail))
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
