@@ -154,6 +154,48 @@ int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, doubl
 int ilqr_initialize_rollout_candidates_device(ilqr_handle* h, int32_t candidates, double violation_weight, const double* d_x1, const double* d_u,
                                               int32_t* d_chosen, double* d_cost, double* d_max_violation, int32_t* d_first_nonfinite);
 
+/* The same with the candidates DRAWN ON THE DEVICE around a base sequence — a sampling (MPPI-style) warm start without a host
+ * array of candidates. Candidate 0 of instance b is base_u[b] itself (copied); candidate s >= 1 is
+ *     u[b][s][t][j] = base_u[b][t][j] + sigma[j] · z(seed, first_instance + b, s, t, j)     (product and sum rounded separately)
+ *     z(seed, b, s, t, j):  key = seed ^ (b·2^40 + s·2^24 + t·2^4 + j),  h1 = splitmix64(key),  h2 = splitmix64(h1),
+ *                           U(h) = ((h >> 11) + 0.5) / 2^53,  z = sqrt(−2 · log(U(h1))) · cos(6.283185307179586 · U(h2))
+ * (t the 0-based step, j the action component; on a sharded handle b counts over the whole batch). Scores, eligibility, the tie
+ * rule, chosen and the "candidate 0 when nobody is eligible" rule are those of ilqr_initialize_rollout_candidates. What is
+ * installed: ILQR_SAMPLE_PICK: the winner (the base for chosen == −1); ILQR_SAMPLE_BLEND: base + sigma_j · Σ_s w_s · z(b, s, t, j),
+ * summed in ascending s, with w_s = exp(−(score_s − score_min) / temperature) for eligible s, 0 otherwise, divided by their sum
+ * (the base when chosen == −1). Afterwards the handle is in exactly the state ilqr_initialize_rollout(h, x1, u_installed) leaves
+ * it in (ilqr_initialize_rollout_resident replays it); policy, duals, scalars, trace and timing are untouched. x1 == NULL / base_u
+ * == NULL: the handle's resident inputs — after ilqr_shift_horizon: the shifted start and guess. weights: blend: w; pick: 1 at
+ * chosen, else 0. u_out: the candidates as drawn. sigma is a HOST pointer in both forms. Refused (ILQR_ERR_INVALID) without
+ * touching the GPU: candidates < 1 or > 65536, an unknown mode, null sigma or a negative or non-finite entry of it, a negative or
+ * non-finite violation_weight, blend with a temperature that is not finite and > 0, first_instance < 0 or first_instance + batch
+ * > 2^23, T − 1 > 2^20, nu > 16, a null handle, a NULL x1 or base_u on a handle without resident inputs. Host form: stages through
+ * device buffers the handle owns and reuses, works on a sharded handle, synchronous. Device form: every pointer but sigma a device
+ * pointer on the handle's device, asynchronous on the handle's stream; refused on a sharded handle. */
+#define ILQR_SAMPLE_PICK 0
+#define ILQR_SAMPLE_BLEND 1
+int ilqr_sample_rollout_candidates(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance,
+                                   const double* sigma,         /* HOST [nu], finite, >= 0 */
+                                   double violation_weight, double temperature,
+                                   const double* x1,            /* NULL, or [B][nx] */
+                                   const double* base_u,        /* NULL, or [B][T-1][nu] */
+                                   int32_t* chosen,             /* NULL, or [B] */
+                                   double* cost,                /* NULL, or [B][S] */
+                                   double* max_violation,       /* NULL, or [B][S] */
+                                   int32_t* first_nonfinite,    /* NULL, or [B][S] */
+                                   double* weights,             /* NULL, or [B][S] */
+                                   double* u_out);              /* NULL, or [B][S][T-1][nu] */
+int ilqr_sample_rollout_candidates_device(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance,
+                                          const double* sigma, double violation_weight, double temperature,
+                                          const double* d_x1, const double* d_base_u, int32_t* d_chosen, double* d_cost,
+                                          double* d_max_violation, int32_t* d_first_nonfinite, double* d_weights, double* d_u_out);
+/* z of the definition above on the host, without a device: z[b][s][t][j] for b < batch (instance first_instance + b), s <
+ * candidates, t < steps, j < nu; row s == 0 is zero. The device draws the same integers and evaluates log, sqrt and cos with its
+ * own library: the two agree to a few ulp of |z| <= 8.7. Refused: a null z, batch, candidates, steps or nu < 0, candidates >
+ * 65536, steps > 2^20, nu > 16, first_instance < 0 or first_instance + batch > 2^23. */
+int ilqr_candidate_noise(uint64_t seed, int64_t first_instance, int32_t batch, int32_t candidates, int32_t steps, int32_t nu,
+                         double* z);
+
 /* Receding-horizon shift of a solved handle by k = `steps` control periods, on the device (N = T − 1; x̄, ū, K, θ as the handle
  * holds them when the call is made). Start state: x1'[b] = x1[b] (the measured state) if given, else x̄_k[b]. Parameters (models
  * with user parameters only): θ'_t = θ_{t+k} for t + k <= T−1; the remaining k rows are w_tail[b][t − (T−k)] if given, else

@@ -122,6 +122,12 @@ SYMBOLS = {
     "ilqr_initialize_rollout_candidates": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, c_double_p, c_double_p, C.POINTER(C.c_int32),
                                                      c_double_p, c_double_p, C.POINTER(C.c_int32)]),
     "ilqr_initialize_rollout_candidates_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_double] + [C.c_void_p] * 6),
+    "ilqr_sample_rollout_candidates": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, c_double_p, C.c_double, C.c_double,
+                                                 c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, C.POINTER(C.c_int32),
+                                                 c_double_p, c_double_p]),
+    "ilqr_sample_rollout_candidates_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, c_double_p, C.c_double, C.c_double]
+                                              + [C.c_void_p] * 8),
+    "ilqr_candidate_noise": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
     "ilqr_shift_horizon": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p]),
     "ilqr_shift_horizon_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "ilqr_solve": (C.c_int, [C.c_void_p]),

@@ -200,6 +200,56 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_initialize_rollout_candidates_device(self._h, int(candidates), float(violation_weight), vp(d_x1_ptr), vp(d_u_ptr),
                                                                         vp(d_chosen_ptr), vp(d_cost_ptr), vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr)))
 
+    _SAMPLE_MODES = {"pick": 0, "blend": 1}
+
+    def _sample_arguments(self, sigma, candidates, mode):
+        if mode not in self._SAMPLE_MODES:
+            raise ValueError('mode must be "pick" or "blend"')
+        sigma = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma, dtype=np.float64), (self.nu,)))
+        return sigma, int(candidates), self._SAMPLE_MODES[mode]
+
+    def sample_rollout_candidates_(self, sigma, candidates, seed=0, mode="pick", temperature=1.0, violation_weight=0.0, x1=None, base_u=None,
+                                   first_instance=0, return_candidates=False):
+        """initialize_rollout_ from candidates drawn on the device around a base sequence (ilqr_sample_rollout_candidates): candidate 0
+        is base_u [B, T-1, nu] itself, candidate s >= 1 is base_u + sigma[j] · z with z = candidate_noise(seed, first_instance + b, s, t, j).
+        x1 / base_u = None: the handle's resident inputs (after shift_horizon_: the shifted start and guess). Scores and choice as
+        initialize_rollout_candidates_; mode="pick" installs the winner, mode="blend" base_u + sigma · Σ_s w_s z_s with the softmin
+        weights w_s ∝ exp(−(score_s − score_min) / temperature) over the eligible candidates. Returns a dict with chosen [B], cost,
+        max_violation, first_nonfinite, weights [B, S] and, with return_candidates, u [B, S, T-1, nu]: the candidates as drawn."""
+        sigma, S, mode = self._sample_arguments(sigma, candidates, mode)
+        if x1 is not None:
+            x1 = np.ascontiguousarray(x1, dtype=np.float64)
+            if x1.shape != (self.B, self.nx):
+                raise ValueError("x1 must have shape [B, nx]")
+        if base_u is not None:
+            base_u = np.ascontiguousarray(base_u, dtype=np.float64)
+            if base_u.shape != (self.B, self.T - 1, self.nu):
+                raise ValueError("base_u must have shape [B, T-1, nu]")
+        if S < 1:
+            raise ValueError("candidates must be >= 1")
+        i32 = C.POINTER(C.c_int32)
+        out = dict(chosen=np.empty(self.B, dtype=np.int32), cost=np.empty((self.B, S)), max_violation=np.empty((self.B, S)),
+                   first_nonfinite=np.empty((self.B, S), dtype=np.int32), weights=np.empty((self.B, S)))
+        if return_candidates:
+            out["u"] = np.empty((self.B, S, self.T - 1, self.nu))
+        _ffi.check(_ffi.lib().ilqr_sample_rollout_candidates(
+            self._h, S, mode, int(seed), int(first_instance), _p(sigma), float(violation_weight), float(temperature),
+            _p(x1) if x1 is not None else None, _p(base_u) if base_u is not None else None, out["chosen"].ctypes.data_as(i32), _p(out["cost"]),
+            _p(out["max_violation"]), out["first_nonfinite"].ctypes.data_as(i32), _p(out["weights"]), _p(out["u"]) if return_candidates else None))
+        return out
+
+    def sample_rollout_candidates_device_(self, sigma, candidates, seed=0, mode="pick", temperature=1.0, violation_weight=0.0, d_x1_ptr=None,
+                                          d_base_u_ptr=None, first_instance=0, d_chosen_ptr=None, d_cost_ptr=None, d_max_violation_ptr=None,
+                                          d_first_nonfinite_ptr=None, d_weights_ptr=None, d_u_out_ptr=None):
+        """The same with raw device pointers on the handle's device (None = the resident input / not wanted); sigma stays a host
+        array; asynchronous on the handle's stream."""
+        sigma, S, mode = self._sample_arguments(sigma, candidates, mode)
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_sample_rollout_candidates_device(
+            self._h, S, mode, int(seed), int(first_instance), _p(sigma), float(violation_weight), float(temperature), vp(d_x1_ptr), vp(d_base_u_ptr),
+            vp(d_chosen_ptr), vp(d_cost_ptr), vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr), vp(d_weights_ptr), vp(d_u_out_ptr)))
+
     _TAILS = {"hold": 0, "zero": 1}
 
     def _shift_arguments(self, steps, tail):
@@ -459,6 +509,14 @@ class Solver:
 
 
 # free-function spellings of the reference's exports (src/IterativeLQR.jl:40-45)
+def candidate_noise(seed, batch, candidates, steps, nu, first_instance=0):
+    """z [batch, candidates, steps, nu] of the candidates Solver.sample_rollout_candidates_ draws (ilqr_candidate_noise): the host twin
+    of the device's generator, a pure function of (seed, first_instance + b, s, t, j); row s = 0 is zero. Needs no device."""
+    z = np.empty((int(batch), int(candidates), int(steps), int(nu)))
+    _ffi.check(_ffi.lib().ilqr_candidate_noise(int(seed), int(first_instance), int(batch), int(candidates), int(steps), int(nu), _p(z)))
+    return z
+
+
 def initialize_controls_(solver, u):
     solver.initialize_controls_(u)
 

@@ -141,6 +141,10 @@ struct ilqr_handle {
     // ilqr_shift_horizon: the device staging of x1 and w_tail (host form) and of the shifted parameters θ' of the whole batch,
     // which are read out of the workspace before a second launch writes them back — grown on demand and reused
     Stage shift[3];
+    // ilqr_sample_rollout_candidates: the device staging of the weights and of the candidates as drawn (host form; the weights also
+    // when a blend's caller does not ask for them) and of sigma, with the host copy of sigma the asynchronous upload reads
+    Stage samp[3];
+    std::vector<double> sample_sigma;
 };
 
 namespace {
@@ -362,6 +366,25 @@ int ilqr_synthetic_inputs(const char* model, int32_t T, uint64_t seed, int64_t f
     return ILQR_OK;
 }
 
+// the host twin of ilqr::sample_z (ilqr_device_sample.hpp): the same key, mix and U; libm's log, sqrt and cos
+int ilqr_candidate_noise(uint64_t seed, int64_t first_instance, int32_t batch, int32_t candidates, int32_t steps, int32_t nu, double* z) {
+#pragma clang fp contract(off)
+    if (!z || batch < 0 || candidates < 0 || steps < 0 || nu < 0) return fail(ILQR_ERR_INVALID, "ilqr_candidate_noise: bad argument");
+    if (candidates > ilqr::SAMPLE_MAX_CANDIDATES || steps > ilqr::SAMPLE_MAX_STEPS || nu > ilqr::SAMPLE_MAX_NU)
+        return fail(ILQR_ERR_INVALID, "ilqr_candidate_noise: candidates <= 65536, steps <= 2^20 and nu <= 16 (the key's bit fields)");
+    if (first_instance < 0 || first_instance + (int64_t)batch > ilqr::SAMPLE_MAX_INSTANCES)
+        return fail(ILQR_ERR_INVALID, "ilqr_candidate_noise: first_instance >= 0 and first_instance + batch <= 2^23 (the key's bit fields)");
+    for (int32_t b = 0; b < batch; ++b)
+        for (int32_t s = 0; s < candidates; ++s)
+            for (int32_t t = 0; t < steps; ++t)
+                for (int32_t j = 0; j < nu; ++j) {
+                    const uint64_t h1 = ilqr::sample_mix(ilqr::sample_key(seed, first_instance + b, s, t, j)), h2 = ilqr::sample_mix(h1);
+                    const double r = std::sqrt(-2.0 * std::log(ilqr::sample_unif(h1)));
+                    z[(((size_t)b * candidates + s) * steps + t) * nu + j] = s == 0 ? 0.0 : r * std::cos(6.283185307179586 * ilqr::sample_unif(h2));
+                }
+    return ILQR_OK;
+}
+
 int ilqr_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -508,6 +531,7 @@ int ilqr_destroy(ilqr_handle* h) {
     for (auto& st : h->pol) if (st.p) hipFree(st.p);
     for (auto& st : h->cand) if (st.p) hipFree(st.p);
     for (auto& st : h->shift) if (st.p) hipFree(st.p);
+    for (auto& st : h->samp) if (st.p) hipFree(st.p);
     if (h->trace) hipFree(h->trace);
     if (h->qv) hipFree(h->qv);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1062,6 +1086,110 @@ int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, doubl
     if (rc != ILQR_OK) return rc;
     void* host[5] = {nullptr, cost, max_violation, first_nonfinite, chosen};
     for (int i = 1; i < 5; ++i)
+        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ILQR_OK;
+}
+
+// ---- candidates drawn on the device around a base sequence (ilqr_device_sample.hpp), then the existing init_rollout on what was installed
+// everything that can be refused without touching the GPU; what needs no handle comes first
+static int sample_check(const ilqr_handle* h, int32_t candidates, int32_t mode, int64_t first_instance, const double* sigma, double violation_weight,
+                        double temperature, const double* x1, const double* base_u, const char* who) {
+    const std::string me(who);
+    if (candidates < 1 || candidates > ilqr::SAMPLE_MAX_CANDIDATES) return fail(ILQR_ERR_INVALID, me + ": candidates must lie in 1 .. 65536");
+    if (mode != ILQR_SAMPLE_PICK && mode != ILQR_SAMPLE_BLEND) return fail(ILQR_ERR_INVALID, me + ": unknown mode");
+    if (!sigma) return fail(ILQR_ERR_INVALID, me + ": null sigma");
+    if (!(sigma[0] >= 0.0) || !std::isfinite(sigma[0])) return fail(ILQR_ERR_INVALID, me + ": sigma must be finite and >= 0");
+    if (!(violation_weight >= 0.0) || !std::isfinite(violation_weight)) return fail(ILQR_ERR_INVALID, me + ": violation_weight must be finite and >= 0");
+    if (mode == ILQR_SAMPLE_BLEND && (!(temperature > 0.0) || !std::isfinite(temperature))) return fail(ILQR_ERR_INVALID, me + ": temperature must be finite and > 0");
+    if (first_instance < 0 || first_instance >= ilqr::SAMPLE_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance must lie in 0 .. 2^23 - 1");
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (h->L.nu > ilqr::SAMPLE_MAX_NU) return fail(ILQR_ERR_INVALID, me + ": more than 16 action components");
+    for (int j = 0; j < h->L.nu; ++j)
+        if (!(sigma[j] >= 0.0) || !std::isfinite(sigma[j])) return fail(ILQR_ERR_INVALID, me + ": sigma must be finite and >= 0");
+    if (h->L.T - 1 > ilqr::SAMPLE_MAX_STEPS) return fail(ILQR_ERR_INVALID, me + ": more than 2^20 steps");
+    if (first_instance + (int64_t)h->B > ilqr::SAMPLE_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance + batch must not exceed 2^23");
+    bool rx = h->d_x1 != nullptr, ru = h->d_u != nullptr;
+    if (!h->shards.empty()) { rx = ru = true; for (const ilqr_handle* s : h->shards) { rx = rx && s->d_x1; ru = ru && s->d_u; } }
+    if ((!x1 && !rx) || (!base_u && !ru))
+        return fail(ILQR_ERR_INVALID, me + ": NULL x1 / base_u mean the handle's resident inputs, and it holds none yet (no initialize_rollout or shift has run)");
+    return ILQR_OK;
+}
+
+// every pointer but sigma a device pointer on h's device; x1 / base_u may be h->d_x1 / h->d_u themselves. Null outputs are replaced by
+// the handle's own buffers where a kernel needs them.
+static int sample_launch(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance, const double* sigma,
+                         double violation_weight, double temperature, const double* x1, const double* base_u, int32_t* chosen, double* cost,
+                         double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
+    if (!h->vt->launch_sample_candidates) return fail(ILQR_ERR_MODEL, "this model module has no candidate sampling kernel");
+    int rc = resident_inputs(h);
+    if (rc != ILQR_OK) return rc;
+    const size_t BS = (size_t)h->B * (size_t)candidates, nu = (size_t)h->L.nu;
+    if (!cost) { rc = grow(h, h->cand[1], BS * 8); if (rc != ILQR_OK) return rc; cost = (double*)h->cand[1].p; }
+    if (!max_violation) { rc = grow(h, h->cand[2], BS * 8); if (rc != ILQR_OK) return rc; max_violation = (double*)h->cand[2].p; }
+    if (!first_nonfinite) { rc = grow(h, h->cand[3], BS * 4); if (rc != ILQR_OK) return rc; first_nonfinite = (int32_t*)h->cand[3].p; }
+    if (!chosen) { rc = grow(h, h->cand[4], (size_t)h->B * 4); if (rc != ILQR_OK) return rc; chosen = (int32_t*)h->cand[4].p; }
+    if (!weights && mode == ILQR_SAMPLE_BLEND) { rc = grow(h, h->samp[0], BS * 8); if (rc != ILQR_OK) return rc; weights = (double*)h->samp[0].p; }
+    rc = grow(h, h->samp[2], nu * 8);
+    if (rc != ILQR_OK) return rc;
+    h->sample_sigma.assign(sigma, sigma + nu);        // the caller's array may go away before the (asynchronous) copy has read it
+    HIP_TRY(hipMemcpyAsync(h->samp[2].p, h->sample_sigma.data(), nu * 8, hipMemcpyHostToDevice, h->stream));
+    ilqr::SampleArgs a;
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = candidates; a.constrained = h->constrained;
+    a.waves = (candidates + 63) / 64 > 4 ? 4 : (candidates + 63) / 64;
+    a.weight = violation_weight; a.x1 = x1 ? x1 : h->d_x1; a.u = nullptr; a.cost = cost; a.viol = max_violation; a.nonfinite = first_nonfinite; a.chosen = chosen;
+    a.r_x1 = h->d_x1; a.r_u = h->d_u;
+    a.seed = seed; a.b0 = first_instance; a.sigma = (const double*)h->samp[2].p; a.base = base_u ? base_u : h->d_u; a.u_out = u_out; a.weights = weights;
+    a.mode = mode; a.temperature = temperature;
+    if (h->vt->launch_sample_candidates(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "candidate sampling launch failed");
+    return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);       // the code that defines the installed state
+}
+
+int ilqr_sample_rollout_candidates_device(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance, const double* sigma,
+                                          double violation_weight, double temperature, const double* x1, const double* base_u, int32_t* chosen,
+                                          double* cost, double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
+    const int rc = sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates_device");
+    if (rc != ILQR_OK) return rc;
+    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_sample_rollout_candidates (host pointers) on a sharded handle");
+    HIP_TRY(hipSetDevice(h->device));
+    return sample_launch(h, candidates, mode, seed, first_instance, sigma, violation_weight, temperature, x1, base_u, chosen, cost, max_violation,
+                         first_nonfinite, weights, u_out);
+}
+
+int ilqr_sample_rollout_candidates(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance, const double* sigma,
+                                   double violation_weight, double temperature, const double* x1, const double* base_u, int32_t* chosen,
+                                   double* cost, double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
+    int rc = sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates");
+    if (rc != ILQR_OK) return rc;
+    const size_t S = (size_t)candidates, N = (size_t)h->L.T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        const size_t o = lo * S;
+        return ilqr_sample_rollout_candidates(s, candidates, mode, seed, first_instance + (int64_t)lo, sigma, violation_weight, temperature,
+                                              x1 ? x1 + lo * n : nullptr, base_u ? base_u + lo * N * m : nullptr, chosen ? chosen + lo : nullptr,
+                                              cost ? cost + o : nullptr, max_violation ? max_violation + o : nullptr,
+                                              first_nonfinite ? first_nonfinite + o : nullptr, weights ? weights + o : nullptr,
+                                              u_out ? u_out + o * N * m : nullptr); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    rc = resident_inputs(h);
+    if (rc != ILQR_OK) return rc;
+    const size_t B = (size_t)h->B, BS = B * S;
+    const size_t bytes[6] = {cost ? BS * 8 : 0, max_violation ? BS * 8 : 0, first_nonfinite ? BS * 4 : 0, chosen ? B * 4 : 0, weights ? BS * 8 : 0,
+                             u_out ? BS * N * m * 8 : 0};
+    ilqr_handle::Stage* st[6] = {&h->cand[1], &h->cand[2], &h->cand[3], &h->cand[4], &h->samp[0], &h->samp[1]};
+    void* d[6];
+    for (int i = 0; i < 6; ++i) {
+        rc = grow(h, *st[i], bytes[i]);
+        if (rc != ILQR_OK) return rc;
+        d[i] = bytes[i] ? st[i]->p : nullptr;
+    }
+    // the caller's x1 and base go straight into the resident inputs: the installation works in place
+    if (x1) HIP_TRY(hipMemcpyAsync(h->d_x1, x1, B * n * 8, hipMemcpyHostToDevice, h->stream));
+    if (base_u) HIP_TRY(hipMemcpyAsync(h->d_u, base_u, B * N * m * 8, hipMemcpyHostToDevice, h->stream));
+    rc = sample_launch(h, candidates, mode, seed, first_instance, sigma, violation_weight, temperature, h->d_x1, h->d_u, (int32_t*)d[3], (double*)d[0],
+                       (double*)d[1], (int32_t*)d[2], (double*)d[4], (double*)d[5]);
+    if (rc != ILQR_OK) return rc;
+    void* host[6] = {cost, max_violation, first_nonfinite, chosen, weights, u_out};
+    for (int i = 0; i < 6; ++i)
         if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;

@@ -2323,11 +2323,12 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_packed.hpp"
 #include "ilqr_device_policy.hpp"
 #include "ilqr_device_candidates.hpp"
+#include "ilqr_device_sample.hpp"
 #include "ilqr_device_shift.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 14   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 15   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2353,6 +2354,9 @@ extern "C" struct ilqr_model_vtable {
     int (*launch_candidates)(const ilqr::CandArgs* a, void* stream);
     // receding-horizon shift of the solved trajectory (and of θ) into the resident inputs (ilqr_device_shift.hpp)
     int (*launch_shift)(const ilqr::ShiftArgs* a, void* stream);
+    // candidate initial guesses drawn on the device: scoring with the candidates generated in place, the weights, the installation
+    // of the winner or of the blend into the resident inputs (ilqr_device_sample.hpp)
+    int (*launch_sample_candidates)(const ilqr::SampleArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2413,7 +2417,7 @@ struct ModelModule {
                                              &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
-                                             &launch_candidates<M>, &launch_shift<M>};
+                                             &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>};
         return &vt;
     }
 };

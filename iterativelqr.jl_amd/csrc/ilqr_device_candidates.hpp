@@ -59,8 +59,12 @@ struct CandDims {
     static constexpr size_t lds_bytes(int waves) { return sizeof(double) * (size_t)(TH + waves * TILE); }
 };
 
-template <class M>
-__global__ __launch_bounds__(256) void candidates_score_kernel(CandArgs a) {
+// GEN (ilqr_device_sample.hpp): the candidates are drawn where they are loaded here — the arguments are SampleArgs, a tile element
+// comes from sample_u (found at instantiation) and is stored to u_out when the caller wants the candidates as drawn
+template <bool GEN> struct CandArgsFor { typedef CandArgs type; };
+
+template <class M, bool GEN = false>
+__global__ __launch_bounds__(256) void candidates_score_kernel(typename CandArgsFor<GEN>::type a) {
     typedef CandDims<M> D;
     constexpr int n = M::NX, m = M::NU, NW = M::NW, ncs = M::NCS, nct = M::NCT;
     extern __shared__ __attribute__((aligned(16))) double cand_lds[];
@@ -86,7 +90,12 @@ __global__ __launch_bounds__(256) void candidates_score_kernel(CandArgs a) {
         for (int k = 0; k < D::PASSES; ++k) {
             const int r = r0 + k * (64 / D::WU);
             const int sr = s_wave + r < S ? s_wave + r : S - 1;
-            pre[k] = lu < cu ? a.u[(((size_t)b * S + sr) * N + tb) * m + lu] : 0.0;
+            if constexpr (GEN) {
+                pre[k] = lu < cu ? sample_u(a, b, sr, tb + lu / m, lu % m) : 0.0;
+                if (a.u_out && lu < cu && s_wave + r < S) a.u_out[(((size_t)b * S + sr) * N + tb) * m + lu] = pre[k];
+            } else {
+                pre[k] = lu < cu ? a.u[(((size_t)b * S + sr) * N + tb) * m + lu] : 0.0;
+            }
         }
     };
     auto park = [&]() {
@@ -160,8 +169,8 @@ __global__ __launch_bounds__(256) void candidates_score_kernel(CandArgs a) {
     }
 }
 
-template <class M>
-__global__ __launch_bounds__(64) void candidates_score_large_kernel(CandArgs a) {
+template <class M, bool GEN = false>
+__global__ __launch_bounds__(64) void candidates_score_large_kernel(typename CandArgsFor<GEN>::type a) {
     constexpr int n = M::NX, m = M::NU, NW = M::NW, ncs = M::NCS, nct = M::NCT;
     __shared__ double sx[n], su[m], sw[cdim<NW>::v];
     const Layout& L = a.L;
@@ -171,11 +180,21 @@ __global__ __launch_bounds__(64) void candidates_score_large_kernel(CandArgs a) 
     const size_t bs = (size_t)b * S + s;
     const double* g = a.ws + (size_t)b * (size_t)L.stride;
     const double* us = a.u + bs * (size_t)N * m;
+    // action `lane` of step t: loaded, or (GEN) drawn and, when the caller wants the candidates as drawn, stored
+    auto action = [&](int t) {
+        if constexpr (GEN) {
+            const double v = sample_u(a, b, s, t, lane);
+            if (a.u_out) a.u_out[(bs * (size_t)N + t) * m + lane] = v;
+            return v;
+        } else {
+            return us[(size_t)t * m + lane];
+        }
+    };
     DynAff<M> aff;
     aff.init(lane);
     const int xrow = DynAff<M>::SPLIT ? (lane & 31) : lane;
     double xl = xrow < n ? a.x1[(size_t)b * n + xrow] : 0.0;
-    double ul = (lane < m && N > 0) ? us[lane] : 0.0;
+    double ul = (lane < m && N > 0) ? action(0) : 0.0;
     double J = 0.0, viol = 0.0;
     int nf = -1;
     if (lane == 0) sw[0] = 0.0;
@@ -185,7 +204,7 @@ __global__ __launch_bounds__(64) void candidates_score_large_kernel(CandArgs a) 
         for (int i = lane; i < NW; i += 64) sw[i] = g[L.w + t * NW + i];
         wave_lds_fence();
         policy_wave_sync();
-        const double u_next = (lane < m && t + 1 < N) ? us[(size_t)(t + 1) * m + lane] : 0.0;
+        const double u_next = (lane < m && t + 1 < N) ? action(t + 1) : 0.0;
         double xa[n], w[cdim<NW>::v];
         bool fin = true;
 #pragma unroll
@@ -236,24 +255,26 @@ __device__ __forceinline__ void cand_take_better(int& ok, double& score, int& id
     idx = take ? qidx : idx;
 }
 
-// One workgroup per instance. Templated on the model only so that every module carries its own copy (the kernel reads nothing
-// of M but the dimensions).
-template <class M>
-__global__ __launch_bounds__(CAND_SELECT_THREADS) void candidates_select_kernel(CandArgs a) {
-    constexpr int n = M::NX, m = M::NU;
+// score of candidate bs = b · S + s; false: not eligible
+__device__ __forceinline__ bool cand_score(const CandArgs& a, size_t bs, double& sc) {
+    const double c = a.cost[bs];
+    sc = a.weight == 0.0 ? c : __dadd_rn(c, __dmul_rn(a.weight, a.viol[bs]));
+    return (fabs(sc) < __builtin_huge_val()) && a.nonfinite[bs] == -1;
+}
+
+// The best candidate of instance b under that order, by a workgroup of CAND_SELECT_THREADS threads (every thread calls it and gets
+// the result): ok = 0 when nobody is eligible.
+__device__ __forceinline__ void cand_best(const CandArgs& a, int b, int& ok, double& score, int& idx) {
     constexpr int W = CAND_SELECT_THREADS / 64;
     __shared__ int part_ok[W], part_idx[W];
     __shared__ double part_score[W];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, S = a.S, N = a.L.T - 1;
-    if (b >= a.B) return;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, S = a.S;
     // an ineligible candidate carries score +Inf: the order never compares a NaN
-    int ok = 0, idx = 0x7fffffff;
-    double score = __builtin_huge_val();
+    ok = 0; idx = 0x7fffffff;
+    score = __builtin_huge_val();
     for (int s = tid; s < S; s += CAND_SELECT_THREADS) {
-        const size_t bs = (size_t)b * S + s;
-        const double c = a.cost[bs];
-        const double sc = a.weight == 0.0 ? c : __dadd_rn(c, __dmul_rn(a.weight, a.viol[bs]));
-        const bool el = (fabs(sc) < __builtin_huge_val()) && a.nonfinite[bs] == -1;
+        double sc;
+        const bool el = cand_score(a, (size_t)b * S + s, sc);
         cand_take_better(ok, score, idx, el ? 1 : 0, el ? sc : __builtin_huge_val(), s);
     }
 #pragma unroll
@@ -267,6 +288,18 @@ __global__ __launch_bounds__(CAND_SELECT_THREADS) void candidates_select_kernel(
     ok = part_ok[0]; score = part_score[0]; idx = part_idx[0];
 #pragma unroll
     for (int v = 1; v < W; ++v) cand_take_better(ok, score, idx, part_ok[v], part_score[v], part_idx[v]);
+}
+
+// One workgroup per instance. Templated on the model only so that every module carries its own copy (the kernel reads nothing
+// of M but the dimensions).
+template <class M>
+__global__ __launch_bounds__(CAND_SELECT_THREADS) void candidates_select_kernel(CandArgs a) {
+    constexpr int n = M::NX, m = M::NU;
+    const int b = blockIdx.x, tid = threadIdx.x, S = a.S, N = a.L.T - 1;
+    if (b >= a.B) return;
+    int ok, idx;
+    double score;
+    cand_best(a, b, ok, score, idx);
     const int win = ok ? idx : 0;                 // nobody eligible: candidate 0, so the handle's state is defined
     const double* src = a.u + ((size_t)b * S + win) * (size_t)N * m;
     double* dst = a.r_u + (size_t)b * N * m;

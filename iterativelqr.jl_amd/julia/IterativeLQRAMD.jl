@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, shift_horizon!,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 const LIB = Ref{String}(joinpath(@__DIR__, "..", "lib", "libilqr_hip.so"))
@@ -136,6 +136,41 @@ function initialize_rollout_candidates!(s::Solver, x1::Matrix{Float64}, u::Array
                 (Ptr{Cvoid}, Int32, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
                 s.handle, Int32(S), violation_weight, x1, u, chosen, cost, viol, nonfinite))
     return chosen .+ Int32(1), cost, viol, nonfinite
+end
+
+# initialize_rollout! from candidates DRAWN ON THE DEVICE around a base sequence (ilqr_sample_rollout_candidates): candidate 1 is
+# base_u :: (nu, T-1, B) itself, candidate s >= 2 is base_u + sigma[j] · z with z = candidate_noise(...) (0-based indices in the key).
+# x1 / base_u = nothing: the handle's resident inputs (after shift_horizon!: the shifted start and guess). mode = :pick installs the
+# winner, :blend base_u + sigma · Σ_s w_s z_s with the softmin weights w_s ∝ exp(−(score_s − score_min) / temperature). Returns
+# (chosen, cost, max_violation, first_nonfinite, weights, u): chosen 1-based, 0 when no candidate was eligible; u :: (nu, T-1, S, B) or
+# nothing without return_candidates.
+function sample_rollout_candidates!(s::Solver, sigma::Vector{Float64}, candidates::Integer; seed::Integer = 0, mode::Symbol = :pick,
+                                    temperature::Float64 = 1.0, violation_weight::Float64 = 0.0, x1::Union{Nothing,Matrix{Float64}} = nothing,
+                                    base_u::Union{Nothing,Array{Float64,3}} = nothing, first_instance::Integer = 0, return_candidates::Bool = false)
+    @assert length(sigma) == s.nu && candidates >= 1 && (mode === :pick || mode === :blend)
+    @assert x1 === nothing || size(x1) == (s.nx, s.B)
+    @assert base_u === nothing || size(base_u) == (s.nu, s.T - 1, s.B)
+    S = Int(candidates)
+    chosen = Vector{Int32}(undef, s.B)
+    cost = Array{Float64,2}(undef, S, s.B); viol = Array{Float64,2}(undef, S, s.B); nonfinite = Array{Int32,2}(undef, S, s.B)
+    weights = Array{Float64,2}(undef, S, s.B)
+    u = return_candidates ? Array{Float64,4}(undef, s.nu, s.T - 1, S, s.B) : nothing
+    nul = Ptr{Float64}(C_NULL)
+    check(ccall((:ilqr_sample_rollout_candidates, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, UInt64, Int64, Ptr{Float64}, Float64, Float64, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, Int32(S), Int32(mode === :pick ? 0 : 1), UInt64(seed), Int64(first_instance), sigma, violation_weight, temperature,
+                x1 === nothing ? nul : x1, base_u === nothing ? nul : base_u, chosen, cost, viol, nonfinite, weights, u === nothing ? nul : u))
+    return chosen .+ Int32(1), cost, viol, nonfinite, weights, u
+end
+
+# z of the candidates the device draws, on the host (ilqr_candidate_noise; needs no device): (nu, steps, candidates, batch), the
+# first candidate's slice is zero
+function candidate_noise(seed::Integer, batch::Integer, candidates::Integer, steps::Integer, nu::Integer; first_instance::Integer = 0)
+    z = Array{Float64,4}(undef, nu, steps, candidates, batch)
+    check(ccall((:ilqr_candidate_noise, LIB[]), Cint, (UInt64, Int64, Int32, Int32, Int32, Int32, Ptr{Float64}),
+                UInt64(seed), Int64(first_instance), Int32(batch), Int32(candidates), Int32(steps), Int32(nu), z))
+    return z
 end
 
 # Receding-horizon shift on the device (ilqr_shift_horizon): the solved trajectory moves forward by `steps` control periods and is
