@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import parity_check
+from oracle_sync import SYNC, sync_from_oracle as _sync_from_oracle  # noqa: F401
 from ilqr_amd_loader import load_package
 
 pytestmark = pytest.mark.gpu
@@ -40,27 +41,6 @@ def _oracle_solver(oracle, model, T, x1, ub):
     s = oracle.Solver(pr, oracle.default_options())
     s.initialize_controls(ub); s.initialize_states(xb)
     return pr, s, xb
-
-
-SYNC = ["nominal_states", "nominal_actions", "states", "actions", "jacobian_state", "jacobian_action",
-        "gradient_state", "gradient_action", "hessian_state_state", "hessian_action_action", "hessian_action_state",
-        "K", "k", "violations", "constraint_dual", "constraint_penalty", "active_set"]
-
-
-def _sync_from_oracle(sol, refs, T):
-    """Copy the oracle's state into the GPU handle so that a stage starts from identical inputs."""
-    n, m, B = sol.nx, sol.nu, sol.B
-    for name in SYNC:
-        sol.set_buffer(name, np.stack([r.buffer(name) for r in refs]))
-    g = [r.buffer("gradient") for r in refs]
-    sol.set_buffer("gradient_state_lagrangian", np.stack([v[:(T - 1) * n] for v in g]))
-    sol.set_buffer("gradient_action_lagrangian", np.stack([v[T * n:] for v in g]))
-    sc = sol.buffer("_scalars")
-    for b, r in enumerate(refs):
-        st = r.stats()
-        sc[b, 0], sc[b, 1], sc[b, 2], sc[b, 3] = st.objective, st.max_violation, st.step_size, st.status
-        sc[b, 9] = 0.0      # states_eq_nominal shortcut off: always evaluate both trajectories
-    sol.set_buffer("_scalars", sc)
 
 
 @pytest.mark.parametrize("config", ["particle", "acrobot", "car", "car_goal", "synth32"])
