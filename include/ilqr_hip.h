@@ -220,9 +220,38 @@ int ilqr_shift_horizon(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feed
 int ilqr_shift_horizon_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback,
                               const double* d_x1, const double* d_w_tail);
 
+/* Receding-horizon shift of the augmented-Lagrangian state by k = `steps` control periods, on the device, in place (N = T − 1,
+ * ncs / nct stage / terminal constraint rows; λ = constraint_dual, ρ = constraint_penalty as the handle holds them, C = N·ncs + nct
+ * doubles per instance, stage row t at t·ncs, the terminal rows at N·ncs). Duals: λ'_t = λ_{t+k} for t < N−k (pure copies: signs
+ * of inequality rows are kept); the last k stage rows get λ_{N−1}, the old last stage row (ILQR_DUALS_TAIL_HOLD), or 0
+ * (ILQR_DUALS_TAIL_ZERO); the terminal rows stay where they are — the terminal constraint stays at the end of the horizon.
+ * Penalties, ILQR_DUALS_PENALTY_KEEP: ρ moves exactly as λ does, tail rows under HOLD copy the old last stage row, under ZERO they
+ * get the handle's initial_constraint_penalty; ILQR_DUALS_PENALTY_RESET: every entry of ρ becomes initial_constraint_penalty.
+ * steps == 0 is allowed: KEEP is then the identity, RESET resets ρ only. Nothing else of the handle changes: trajectory, policy, θ,
+ * scalars, trace, timing, resident inputs. The companion of ilqr_shift_horizon, which leaves duals and penalties untouched.
+ * Refused (ILQR_ERR_INVALID) without touching the GPU: a null handle, a handle created unconstrained, steps < 0 or > T−1, an
+ * unknown tail or penalty, steps > 0 on a handle with stage selectors (the rule of ilqr_shift_horizon, for its reason), a handle
+ * that holds no duals yet — duals are held after ilqr_solve / ilqr_solve_warm on a constrained handle, ILQR_STAGE_AL_BEGIN,
+ * ilqr_solve_shared_step or a host write of constraint_penalty through ilqr_set_buffer, until ilqr_reset; on a sharded handle
+ * every shard must hold them. Host form: synchronous, works on a sharded handle. Device form: asynchronous on the handle's stream;
+ * refused on a sharded handle. */
+#define ILQR_DUALS_TAIL_HOLD 0
+#define ILQR_DUALS_TAIL_ZERO 1
+#define ILQR_DUALS_PENALTY_KEEP 0
+#define ILQR_DUALS_PENALTY_RESET 1
+int ilqr_shift_duals(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty);
+int ilqr_shift_duals_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty);
+
 /* solve!(solver) — src/solve.jl:137-143. Asynchronous: enqueues the whole
  * AL/iLQR solve of every instance on the handle's stream. */
 int ilqr_solve(ilqr_handle* h);
+/* ilqr_solve with src/solve.jl:95-103 (λ ← 0, ρ ← ρ0) skipped: the solve uses the duals and penalties the workspace holds, e.g.
+ * those of the last solve moved along by ilqr_shift_duals. reset!(solver.data) (:93) and everything else run unchanged: the
+ * Lagrangian gradient and the scalars are zeroed, outer_iterations counts from 1. This is not a reference behaviour — the reference
+ * opens every constrained solve cold. Every kernel family honours it (hand-over included); asynchronous, sharded-capable and timed
+ * like ilqr_solve. Refused (ILQR_ERR_INVALID): a null handle, a handle created unconstrained, a handle that holds no duals (the
+ * rule above: with ρ = 0 everywhere the solve would silently be the unconstrained one). */
+int ilqr_solve_warm(ilqr_handle* h);
 int ilqr_synchronize(ilqr_handle* h);
 
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):

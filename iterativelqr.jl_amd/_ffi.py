@@ -130,7 +130,10 @@ SYMBOLS = {
     "ilqr_candidate_noise": (C.c_int, [C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_double_p]),
     "ilqr_shift_horizon": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, c_double_p]),
     "ilqr_shift_horizon_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ilqr_shift_duals": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "ilqr_shift_duals_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ilqr_solve": (C.c_int, [C.c_void_p]),
+    "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),
     "ilqr_solve_shared_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.POINTER(C.c_int32)]),
     "ilqr_run_stage": (C.c_int, [C.c_void_p, C.c_int32]),

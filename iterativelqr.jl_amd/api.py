@@ -285,6 +285,37 @@ class Solver:
             return C.c_void_p(p) if p else None
         _ffi.check(_ffi.lib().ilqr_shift_horizon_device(self._h, steps, tail, 1 if feedback else 0, vp(d_x1_ptr), vp(d_w_tail_ptr)))
 
+    _PENALTIES = {"keep": 0, "reset": 1}
+
+    def _duals_arguments(self, steps, tail, penalty):
+        steps, tail = self._shift_arguments(steps, tail)
+        if penalty not in self._PENALTIES:
+            raise ValueError('penalty must be "keep" or "reset"')
+        _ffi.check(_ffi.lib().ilqr_set_options(self._h, C.byref(self.options)))     # ρ0 = options.initial_constraint_penalty
+        return steps, tail, self._PENALTIES[penalty]
+
+    def shift_duals_(self, steps=1, tail="hold", penalty="keep"):
+        """Receding-horizon shift of the duals and penalties on the device (ilqr_shift_duals), the companion of shift_horizon_:
+        λ'_t = λ_{t+steps} for the stage rows that have a source, the last `steps` stage rows get the old last stage row
+        (tail="hold") or 0 ("zero"), the terminal rows stay. penalty="keep": ρ moves as λ does (a "zero" tail gets
+        options.initial_constraint_penalty); "reset": every entry of ρ becomes options.initial_constraint_penalty. Nothing else of
+        the handle changes. Refused on an unconstrained handle and on one that holds no duals yet."""
+        _ffi.check(_ffi.lib().ilqr_shift_duals(self._h, *self._duals_arguments(steps, tail, penalty)))
+
+    def shift_duals_device_(self, steps=1, tail="hold", penalty="keep"):
+        """The same, asynchronous on the handle's stream; not on a handle that spans several devices."""
+        _ffi.check(_ffi.lib().ilqr_shift_duals_device(self._h, *self._duals_arguments(steps, tail, penalty)))
+
+    def solve_warm_(self, sync=True):
+        """solve_ with src/solve.jl:95-103 (λ ← 0, ρ ← ρ0) skipped (ilqr_solve_warm): the solve keeps the duals and penalties the
+        handle holds — those of the last solve, moved along by shift_duals_, or the caller's own written with set_buffer. Everything
+        else is solve_'s: one launch, every kernel variant, outer_iterations counted from 1. Not a reference behaviour. Refused on
+        an unconstrained handle and on one that holds no duals yet (after reset_ ρ is not a solve's)."""
+        _ffi.check(_ffi.lib().ilqr_set_options(self._h, C.byref(self.options)))
+        _ffi.check(_ffi.lib().ilqr_solve_warm(self._h))
+        if sync:
+            self.synchronize()
+
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""
         w = np.ascontiguousarray(w, dtype=np.float64).reshape(self.B, self.T, self.num_user_parameter)

@@ -145,6 +145,9 @@ struct ilqr_handle {
     // when a blend's caller does not ask for them) and of sigma, with the host copy of sigma the asynchronous upload reads
     Stage samp[3];
     std::vector<double> sample_sigma;
+    // ilqr_shift_duals / ilqr_solve_warm: λ, ρ hold the duals of a solve (a constrained solve, the AL_BEGIN stage or a host write of
+    // constraint_penalty since the last reset) — after a reset ρ is not a penalty ladder's and a warm solve would be refused
+    bool has_duals = false;
 };
 
 namespace {
@@ -160,6 +163,7 @@ ilqr::KArgs make_args(const ilqr_handle* h) {
     a.stage_param = 0.0; a.stage_flag = 0;
     a.handover_outer = 0; a.resume = 0; a.handover_live = 0; a.done_counter = h->done_counter;
     a.pool = nullptr; a.pool_mark = 0; a.pool_lds = 0; a.pool_ctl = 0; a.pool_cu = 0; a.cu_slots = nullptr; a.cu_expect = 0;
+    a.warm_duals = 0;
     return a;
 }
 
@@ -564,6 +568,7 @@ int ilqr_reset(ilqr_handle* h) {
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_reset(s); });
     HIP_TRY(hipSetDevice(h->device));
     h->has_policy = false;                            // K, k are zeroed below
+    h->has_duals = false;                             // λ ← 0, and ρ ← 1 is the fresh solver's, not a solve's
     if (ilqr::is_large_model(h->vt->nx, h->vt->nu) && h->vt->nw == 0) {
         // HBM-resident models: zero the trajectories, gradients, gains, duals, scalars and the compact Jacobian / Hessian rows
         // now; the megabyte-sized full Jacobian / Hessian mirrors are rewritten from the compact form when a getter asks
@@ -686,12 +691,13 @@ int ilqr_initialize_rollout_resident(ilqr_handle* h) {
     return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);
 }
 
-int ilqr_solve(ilqr_handle* h) {
-    if (!h) return fail(ILQR_ERR_INVALID, "null handle");
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_solve(s); });      // asynchronous on every device's stream
+// ilqr_solve (warm == 0) and ilqr_solve_warm (warm == 1): one body, the launches differ in KArgs::warm_duals alone
+static int solve_launch(ilqr_handle* h, int warm) {
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return solve_launch(s, warm); });      // asynchronous on every device's stream
     HIP_TRY(hipSetDevice(h->device));
     ilqr::KArgs a = make_args(h);
     a.qv = nullptr;
+    a.warm_duals = warm;                              // (copied into the resume launch's arguments below)
     if (h->trace)      // rows of an earlier, longer solve must not survive
         HIP_TRY(hipMemsetAsync(h->trace, 0, (size_t)h->B * h->trace_cap * ilqr::TRACE_W * 8, h->stream));
     if (h->vt->launch_mirror) h->full_stale = true;   // the kernel works on the compact Jacobian / Hessian rows
@@ -728,12 +734,31 @@ int ilqr_solve(ilqr_handle* h) {
         return drop(fail(ILQR_ERR_HIP, "solve (hand-over resume) launch failed"));
     if (hipEventRecord(e1, h->stream) != hipSuccess) return drop(fail(ILQR_ERR_HIP, "hipEventRecord failed"));
     h->has_policy = true;
+    if (h->constrained) h->has_duals = true;
     h->timing.emplace_back(e0, e1);
     if (h->timing.size() > 4096) {     // long-running callers that never read the timing: keep the newest half
         for (size_t i = 0; i < 2048; ++i) { hipEventDestroy(h->timing[i].first); hipEventDestroy(h->timing[i].second); }
         h->timing.erase(h->timing.begin(), h->timing.begin() + 2048);
     }
     return ILQR_OK;
+}
+
+int ilqr_solve(ilqr_handle* h) {
+    if (!h) return fail(ILQR_ERR_INVALID, "null handle");
+    return solve_launch(h, 0);
+}
+
+static bool holds_duals(const ilqr_handle* h) {
+    if (h->shards.empty()) return h->has_duals;
+    for (const ilqr_handle* s : h->shards) if (!s->has_duals) return false;
+    return true;
+}
+
+int ilqr_solve_warm(ilqr_handle* h) {
+    if (!h) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: null handle");
+    if (!h->constrained) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: the handle was created unconstrained: it has no duals to keep");
+    if (!holds_duals(h)) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: the handle holds no duals yet (no constrained solve, no al_begin stage and no host write of constraint_penalty since the last reset)");
+    return solve_launch(h, 1);
 }
 
 int ilqr_run_stage(ilqr_handle* h, int32_t stage) { return ilqr_run_stage_param(h, stage, 0.0, 0); }
@@ -751,6 +776,7 @@ int ilqr_run_stage_param(ilqr_handle* h, int32_t stage, double param, int32_t fl
     if (h->vt->launch(p.kernel, &a, p.grid, p.lds, h->stream) != 0) return fail(ILQR_ERR_HIP, "stage launch failed (kernel " + std::to_string(p.kernel) + ")");
     if (h->vt->launch_mirror) h->full_stale = true;
     if (stage == ILQR_STAGE_BACKWARD_PASS || stage == ILQR_STAGE_ILQR_SOLVE || stage == ILQR_STAGE_SS_FINISH) h->has_policy = true;
+    if (stage == ILQR_STAGE_AL_BEGIN) h->has_duals = true;      // (ilqr_solve_shared_step opens with this stage)
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
 }
@@ -930,6 +956,7 @@ int ilqr_set_buffer(ilqr_handle* h, const char* name, const double* in) {
     if (!bd) return fail(ILQR_ERR_INVALID, std::string("unknown buffer '") + name + "'");
     const int rc = copy_in(h, bd, in);
     if (rc == ILQR_OK && (bd->offset == h->L.K || bd->offset == h->L.k)) h->has_policy = true;      // the caller's own policy
+    if (rc == ILQR_OK && !std::strcmp(bd->name, "constraint_penalty")) h->has_duals = true;      // the caller's own penalties
     return rc;
 }
 
@@ -1259,6 +1286,43 @@ int ilqr_shift_horizon(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feed
     rc = shift_launch(h, steps, tail, feedback, d[0], d[1]);
     if (rc != ILQR_OK) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller
+    return ILQR_OK;
+}
+
+// ---- receding-horizon shift of the duals and penalties (ilqr_device_duals.hpp)
+// everything that can be refused without touching the GPU
+static int duals_check(const ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty, const char* who) {
+    const std::string me(who);
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (!h->constrained) return fail(ILQR_ERR_INVALID, me + ": the handle was created unconstrained: it has no duals to shift");
+    if (steps < 0 || steps > h->L.T - 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 0 .. T-1");
+    if (tail != ILQR_DUALS_TAIL_HOLD && tail != ILQR_DUALS_TAIL_ZERO) return fail(ILQR_ERR_INVALID, me + ": unknown tail mode");
+    if (penalty != ILQR_DUALS_PENALTY_KEEP && penalty != ILQR_DUALS_PENALTY_RESET) return fail(ILQR_ERR_INVALID, me + ": unknown penalty mode");
+    if (steps > 0 && h->n_sel > 0)
+        return fail(ILQR_ERR_INVALID, me + ": the handle has stage selectors attached: the structure of a lowered problem belongs to horizon positions and cannot be shifted");
+    if (!holds_duals(h)) return fail(ILQR_ERR_INVALID, me + ": the handle holds no duals yet (no constrained solve, no al_begin stage and no host write of constraint_penalty since the last reset)");
+    return ILQR_OK;
+}
+
+int ilqr_shift_duals_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty) {
+    const int rc = duals_check(h, steps, tail, penalty, "ilqr_shift_duals_device");
+    if (rc != ILQR_OK) return rc;
+    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "ilqr_shift_duals_device: a sharded handle has one stream per device: call ilqr_shift_duals on it");
+    if (!h->vt->launch_shift_duals) return fail(ILQR_ERR_MODEL, "this model module has no dual shift kernel");
+    HIP_TRY(hipSetDevice(h->device));
+    ilqr::DualsArgs a;
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.tail = tail; a.penalty = penalty; a.rho0 = h->opt.initial_constraint_penalty;
+    if (h->vt->launch_shift_duals(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "dual shift launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_shift_duals(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty) {
+    int rc = duals_check(h, steps, tail, penalty, "ilqr_shift_duals");
+    if (rc != ILQR_OK) return rc;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_shift_duals(s, steps, tail, penalty); });
+    rc = ilqr_shift_duals_device(h, steps, tail, penalty);
+    if (rc != ILQR_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
 }
 

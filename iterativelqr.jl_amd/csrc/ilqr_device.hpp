@@ -77,6 +77,9 @@ struct KArgs {
     // the same assignment of critical waves to SIMDs: as many distinct SIMDs as the placement allows (pick_roles).
     int* cu_slots;
     int cu_expect;         // workgroups the launch puts on a CU (<= 4)
+    // ilqr_solve_warm: the solve keeps the duals and penalties the workspace holds — λ ← 0, ρ ← ρ0 (src/solve.jl:95-103) is skipped,
+    // reset!(solver.data) (:93) and everything else runs as ever. Read once per solve, where the prologue would fill them. 0 = ilqr_solve.
+    int warm_duals;
 };
 enum { CU_SLOT_CUS = 8 * 8 * 2 * 16, CU_SLOT_INTS = 8 };      // xcc x se x sh x cu of HW_REG_XCC_ID / HW_REG_HW_ID; [0] arrivals, [1..4] their SIMD pairs
 enum { TRACE_W = 8 };   // outer, inner, objective, gradient_norm, max_violation, step_size, status, rollouts
@@ -1865,12 +1868,12 @@ __device__ void al_update(Inst<M>& I, const ilqr_options& opt) {
 //   al_outer = false: a single ilqr_solve! (plain Objective, or the stage test)
 template <class M, bool STORE_VALUE, int SPEC = 0>
 __device__ void solve_loops(Inst<M>& I, const ilqr_options& opt, bool constrained, bool al_outer, int o_start = 1, int it_start = 0,
-                            double obj_prev0 = 0.0) {
+                            double obj_prev0 = 0.0, bool warm_duals = false) {
     if (al_outer && o_start == 1 && it_start == 0) {
-        // reset!(solver.data) (:93, src/data/solver.jl:49-59); λ ← 0, ρ ← ρ0 (:96-103)
+        // reset!(solver.data) (:93, src/data/solver.jl:49-59); λ ← 0, ρ ← ρ0 (:96-103) unless the solve is warm (KArgs::warm_duals)
         I.objective = 0.0; I.max_violation = 0.0; I.status = 0; I.iterations = 0; I.gradient_norm = 0.0;
         zero_lagrangian_gradient<M>(I);
-        for (int i = I.lane; i < I.C; i += 64) {
+        if (!warm_duals) for (int i = I.lane; i < I.C; i += 64) {
             I.lam[i] = 0.0;
             I.rho[i] = opt.initial_constraint_penalty;
         }
@@ -2097,7 +2100,7 @@ __device__ __forceinline__ void solve_instance(const KArgs& a, double* smem, int
     }
     {
         ILQR_PROF_BEGIN();
-        solve_loops<M, false, SPEC>(I, a.opt, a.constrained != 0, a.constrained != 0, o_start, it_start, obj_prev0);
+        solve_loops<M, false, SPEC>(I, a.opt, a.constrained != 0, a.constrained != 0, o_start, it_start, obj_prev0, a.warm_duals != 0);
         ILQR_PROF_END(I, PROF_OTHER);   // total; phases are subtracted on the host
     }
     if (I.lane == 0 && I.wave == 0) {
@@ -2140,7 +2143,7 @@ __global__ __launch_bounds__(64, 2) void solve_kernel_slim(KArgs a) {
     Inst<MS> I;
     inst_setup<MS>(I, a, smem, b);
     I.potrf_info = 0; I.rollouts = 0; I.outer_iterations = 0;
-    solve_loops<MS, false>(I, a.opt, a.constrained != 0, a.constrained != 0);
+    solve_loops<MS, false>(I, a.opt, a.constrained != 0, a.constrained != 0, 1, 0, 0.0, a.warm_duals != 0);
     if (I.lane == 0) I.scal[S_TRACE_LEN] = (double)(I.trace_len < I.trace_cap ? I.trace_len : I.trace_cap);
     inst_writeback<MS>(I, a, smem, b);
 }
@@ -2325,10 +2328,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_candidates.hpp"
 #include "ilqr_device_sample.hpp"
 #include "ilqr_device_shift.hpp"
+#include "ilqr_device_duals.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 15   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 16   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2357,6 +2361,8 @@ extern "C" struct ilqr_model_vtable {
     // candidate initial guesses drawn on the device: scoring with the candidates generated in place, the weights, the installation
     // of the winner or of the blend into the resident inputs (ilqr_device_sample.hpp)
     int (*launch_sample_candidates)(const ilqr::SampleArgs* a, void* stream);
+    // receding-horizon shift of the duals and penalties, in place in the workspace (ilqr_device_duals.hpp)
+    int (*launch_shift_duals)(const ilqr::DualsArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2417,7 +2423,7 @@ struct ModelModule {
                                              &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
-                                             &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>};
+                                             &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>, &launch_shift_duals<M>};
         return &vt;
     }
 };

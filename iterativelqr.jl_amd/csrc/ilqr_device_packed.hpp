@@ -859,12 +859,13 @@ __device__ __forceinline__ void packed_solve_body(const KArgs& a, const int pack
     I.potrf_info = 0; I.rollouts = 0; I.outer = 0; I.delta = 0.0; I.delta_next = 0.0; I.obj_prev = 0.0; I.J_prev = 0.0; I.it = 0; I.trial = 1; I.needB = 0; I.leaving = 0;
     const bool live = I.valid_row;
     if (al_outer) {
-        // reset!(solver.data) (src/solve.jl:93); λ ← 0, ρ ← ρ0 (:96-103)
+        // reset!(solver.data) (src/solve.jl:93); λ ← 0, ρ ← ρ0 (:96-103) unless the solve is warm (KArgs::warm_duals)
         I.objective = 0.0; I.max_violation = 0.0; I.status = 0; I.iterations = 0; I.gradient_norm = 0.0;
         row_fill<M>(I, live, L.Lx, N * n, 0.0);
         row_fill<M>(I, live, L.Lu, N * m, 0.0);
-        row_fill<M>(I, live, L.lam, C, 0.0);
-        row_fill<M>(I, live, L.rho, C, opt.initial_constraint_penalty);
+        const bool cold = live && a.warm_duals == 0;
+        row_fill<M>(I, cold, L.lam, C, 0.0);
+        row_fill<M>(I, cold, L.rho, C, opt.initial_constraint_penalty);
         I.outer = 1;
     }
     I.state = live ? ST_INIT : ST_DONE;

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 const LIB = Ref{String}(joinpath(@__DIR__, "..", "lib", "libilqr_hip.so"))
@@ -187,6 +187,32 @@ function shift_horizon!(s::Solver; steps::Integer = 1, x1::Union{Nothing,Matrix{
     check(ccall((:ilqr_shift_horizon, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
                 s.handle, Int32(steps), Int32(tail === :hold ? 0 : 1), Int32(feedback ? 1 : 0), x1 === nothing ? nul : x1,
                 w_tail === nothing ? nul : w_tail))
+end
+
+# Receding-horizon shift of the duals and penalties on the device (ilqr_shift_duals), the companion of shift_horizon!: λ'_t = λ_{t+steps},
+# the last `steps` stage rows the old last stage row (tail = :hold) or 0 (:zero), the terminal rows stay; penalty = :keep moves ρ as λ
+# (a :zero tail gets initial_constraint_penalty), :reset writes initial_constraint_penalty everywhere. Nothing else changes.
+function shift_duals!(s::Solver; steps::Integer = 1, tail::Symbol = :hold, penalty::Symbol = :keep)
+    @assert 0 <= steps <= s.T - 1 && (tail === :hold || tail === :zero) && (penalty === :keep || penalty === :reset)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    check(ccall((:ilqr_shift_duals, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32, Int32),
+                s.handle, Int32(steps), Int32(tail === :hold ? 0 : 1), Int32(penalty === :keep ? 0 : 1)))
+end
+
+# The same, asynchronous on the handle's stream (not on a handle that spans several devices)
+function shift_duals_device!(s::Solver; steps::Integer = 1, tail::Symbol = :hold, penalty::Symbol = :keep)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    check(ccall((:ilqr_shift_duals_device, LIB[]), Cint, (Ptr{Cvoid}, Int32, Int32, Int32),
+                s.handle, Int32(steps), Int32(tail === :hold ? 0 : 1), Int32(penalty === :keep ? 0 : 1)))
+end
+
+# solve! with src/solve.jl:95-103 (λ ← 0, ρ ← ρ0) skipped: the duals and penalties the handle holds are kept (ilqr_solve_warm).
+# Not a reference behaviour: the reference opens every constrained solve cold.
+function solve_warm!(s::Solver)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    check(ccall((:ilqr_solve_warm, LIB[]), Cint, (Ptr{Cvoid},), s.handle))
+    check(ccall((:ilqr_synchronize, LIB[]), Cint, (Ptr{Cvoid},), s.handle))
+    return nothing
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
