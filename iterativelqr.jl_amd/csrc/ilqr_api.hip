@@ -68,6 +68,8 @@ thread_local std::string g_err;
         if (e_ != hipSuccess)                                                                 \
             return fail(ILQR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));     \
     } while (0)
+// the same for a call that returns one of this file's own codes (and has set the error text)
+#define ILQR_TRY(expr) do { const int rc_ = (expr); if (rc_ != ILQR_OK) return rc_; } while (0)
 
 std::vector<const ilqr_model_vtable*>& registry() {
     static std::vector<const ilqr_model_vtable*> r;
@@ -91,6 +93,12 @@ const ilqr_model_vtable* ilqr::find_model(const char* name) {
 long long ilqr::model_abi_word() { return ILQR_MODEL_ABI_VERSION * 1000 + (long long)sizeof(ilqr::KArgs); }
 using ilqr::fail;
 using ilqr::find_model;
+
+// the stages (ilqr_handle::Stage) of ilqr_handle::pol, ::cand, ::shift and ::samp by name
+enum { POL_X1, POL_W, POL_COST, POL_VIOL, POL_NONFINITE, POL_X, POL_U, POL_STAGES };
+enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
+enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
+enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -131,19 +139,22 @@ struct ilqr_handle {
     // the LAST n_sel parameter columns of every instance, the caller's ilqr_set_parameters fills the first nw - n_sel
     std::vector<double> sel;
     int n_sel = 0;
+    // a device buffer of the MPC-side entry points that grows on demand (grow()) and is reused by later calls
+    struct Stage { void* p = nullptr; size_t cap = 0; };
     // ilqr_rollout_policy: K, k hold a policy (a solve, a backward-pass stage or a host write of K / k since the last reset), and the
-    // device staging of its host form — x1, w, cost, max_violation, first_nonfinite, x, u — which grows on demand and is reused
+    // device staging of its host form
     bool has_policy = false;
-    struct Stage { void* p = nullptr; size_t cap = 0; } pol[7];
-    // ilqr_initialize_rollout_candidates: the device staging of the candidates' u (host form) and the score buffers the caller
-    // did not ask for — u, cost, max_violation, first_nonfinite, chosen — grown on demand and reused
-    Stage cand[5];
+    Stage pol[POL_STAGES];
+    // ilqr_initialize_rollout_candidates: the device staging of the candidates' u (host form) and of the scores — the host form's
+    // outputs, and the handle's own buffers for the scores a caller did not ask for. ilqr_sample_rollout_candidates scores into
+    // the same four.
+    Stage cand[CAND_STAGES];
     // ilqr_shift_horizon: the device staging of x1 and w_tail (host form) and of the shifted parameters θ' of the whole batch,
-    // which are read out of the workspace before a second launch writes them back — grown on demand and reused
-    Stage shift[3];
-    // ilqr_sample_rollout_candidates: the device staging of the weights and of the candidates as drawn (host form; the weights also
-    // when a blend's caller does not ask for them) and of sigma, with the host copy of sigma the asynchronous upload reads
-    Stage samp[3];
+    // which are read out of the workspace before a second launch writes them back
+    Stage shift[SHIFT_STAGES];
+    // ilqr_sample_rollout_candidates: the device staging of the weights (host form, and a blend whose caller does not ask for
+    // them), of the candidates as drawn (host form) and of sigma, with the host copy of sigma the asynchronous upload reads
+    Stage samp[SAMP_STAGES];
     std::vector<double> sample_sigma;
     // ilqr_shift_duals / ilqr_solve_warm: λ, ρ hold the duals of a solve (a constrained solve, the AL_BEGIN stage or a host write of
     // constraint_penalty since the last reset) — after a reset ρ is not a penalty ladder's and a warm solve would be refused
@@ -283,6 +294,73 @@ int each_shard(ilqr_handle* h, F f, bool threaded = false) {
     return ILQR_OK;
 }
 #define SHARDED(h) ((h) && !(h)->shards.empty())
+
+// the handle, or every shard of a sharded one, holds member m (has_policy, has_duals, d_x1, d_u)
+template <class M> bool every_shard_holds(const ilqr_handle* h, M ilqr_handle::*m) {
+    if (h->shards.empty()) return (bool)(h->*m);
+    for (const ilqr_handle* s : h->shards) if (!(s->*m)) return false;
+    return true;
+}
+
+// the refusal of the *_device forms on a sharded handle; host_form: the entry point that takes host pointers
+int refuse_sharded(const char* host_form) {
+    return fail(ILQR_ERR_INVALID, std::string("device pointers belong to one device: call ") + host_form + " (host pointers) on a sharded handle");
+}
+// an optional array of the whole batch as a shard sees it
+template <class T> T* at(T* p, size_t off) { return p ? p + off : nullptr; }
+// waves per workgroup of the kernels that give every sample / candidate of an instance a lane
+int waves_for(int32_t S) { return (S + 63) / 64 > 4 ? 4 : (S + 63) / 64; }
+
+// the inputs the handle keeps in HBM: what init_rollout reads, and what the MPC-side initialisers install in place
+int resident_inputs(ilqr_handle* h) {
+    const size_t bx = (size_t)h->B * h->vt->nx * 8, bu = (size_t)h->B * (h->L.T - 1) * h->vt->nu * 8;
+    if (!h->d_x1) HIP_TRY(hipMalloc((void**)&h->d_x1, bx));
+    if (!h->d_u) HIP_TRY(hipMalloc((void**)&h->d_u, bu));
+    return ILQR_OK;
+}
+
+// the one place that frees and reallocates a stage: not before the stream has finished with the old buffer
+int grow(ilqr_handle* h, ilqr_handle::Stage& st, size_t bytes) {
+    if (bytes <= st.cap) return ILQR_OK;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (st.p) { HIP_TRY(hipFree(st.p)); st.p = nullptr; st.cap = 0; }
+    HIP_TRY(hipMalloc(&st.p, bytes));
+    st.cap = bytes;
+    return ILQR_OK;
+}
+
+// a null output of a *_launch means the handle's own buffer
+template <class T> int own_if_null(ilqr_handle* h, T*& out, ilqr_handle::Stage& st, size_t bytes) {
+    if (out) return ILQR_OK;
+    ILQR_TRY(grow(h, st, bytes));
+    out = (T*)st.p;
+    return ILQR_OK;
+}
+
+// One array of a host form: the stage that holds it on the device, the host array it is uploaded from (an input) or downloaded
+// to (an output), its size. An array the caller did not give has no bytes: it never allocates, and its device pointer is null.
+struct Staged {
+    ilqr_handle::Stage* st; const void* src; void* dst; size_t bytes;
+    template <class T> T* dev() const { return bytes ? (T*)st->p : nullptr; }
+};
+Staged staged_in(ilqr_handle::Stage& st, const void* src, size_t bytes) { return {&st, src, nullptr, src ? bytes : 0}; }
+Staged staged_out(ilqr_handle::Stage& st, void* dst, size_t bytes) { return {&st, nullptr, dst, dst ? bytes : 0}; }
+
+// every stage of a host form grown, then its inputs on their way to the device
+int stage_in(ilqr_handle* h, std::initializer_list<Staged> arrays) {
+    for (const Staged& a : arrays) ILQR_TRY(grow(h, *a.st, a.bytes));
+    for (const Staged& a : arrays)
+        if (a.src && a.bytes) HIP_TRY(hipMemcpyAsync(a.st->p, a.src, a.bytes, hipMemcpyHostToDevice, h->stream));
+    return ILQR_OK;
+}
+
+// its outputs on their way back, and the stream finished: the caller may read them, and reuse the host arrays of the inputs
+int stage_out(ilqr_handle* h, std::initializer_list<Staged> arrays) {
+    for (const Staged& a : arrays)
+        if (a.dst && a.bytes) HIP_TRY(hipMemcpyAsync(a.dst, a.st->p, a.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return ILQR_OK;
+}
 
 // test hook (ilqr_device_math): the scalar routines of ilqr_math.hpp as the device executes them
 __global__ void device_math_kernel(int which, const double* x, double* y, int n) {
@@ -646,7 +724,7 @@ int ilqr_set_parameters(ilqr_handle* h, const double* w) {
 
 int ilqr_initialize_rollout_device(ilqr_handle* h, const double* d_x1, const double* d_u) {
     if (!h || !d_x1 || !d_u) return fail(ILQR_ERR_INVALID, "null argument");
-    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_initialize_rollout (host pointers) on a sharded handle");
+    if (SHARDED(h)) return refuse_sharded("ilqr_initialize_rollout");
     HIP_TRY(hipSetDevice(h->device));
     ilqr::KArgs a = make_args(h);
     a.x1 = d_x1; a.u_in = d_u;
@@ -659,13 +737,11 @@ int ilqr_initialize_rollout(ilqr_handle* h, const double* x1, const double* u) {
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         return ilqr_initialize_rollout(s, x1 + lo * (size_t)h->L.nx, u + lo * (size_t)(h->L.T - 1) * h->L.nu); }, true);
     HIP_TRY(hipSetDevice(h->device));
+    ILQR_TRY(resident_inputs(h));
     const size_t bx = (size_t)h->B * h->vt->nx * 8, bu = (size_t)h->B * (h->L.T - 1) * h->vt->nu * 8;
-    if (!h->d_x1) HIP_TRY(hipMalloc((void**)&h->d_x1, bx));
-    if (!h->d_u) HIP_TRY(hipMalloc((void**)&h->d_u, bu));
     HIP_TRY(hipMemcpyAsync(h->d_x1, x1, bx, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->d_u, u, bu, hipMemcpyHostToDevice, h->stream));
-    int rc = ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(ilqr_initialize_rollout_device(h, h->d_x1, h->d_u));
     HIP_TRY(hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller
     return ILQR_OK;
 }
@@ -748,16 +824,10 @@ int ilqr_solve(ilqr_handle* h) {
     return solve_launch(h, 0);
 }
 
-static bool holds_duals(const ilqr_handle* h) {
-    if (h->shards.empty()) return h->has_duals;
-    for (const ilqr_handle* s : h->shards) if (!s->has_duals) return false;
-    return true;
-}
-
 int ilqr_solve_warm(ilqr_handle* h) {
     if (!h) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: null handle");
     if (!h->constrained) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: the handle was created unconstrained: it has no duals to keep");
-    if (!holds_duals(h)) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: the handle holds no duals yet (no constrained solve, no al_begin stage and no host write of constraint_penalty since the last reset)");
+    if (!every_shard_holds(h, &ilqr_handle::has_duals)) return fail(ILQR_ERR_INVALID, "ilqr_solve_warm: the handle holds no duals yet (no constrained solve, no al_begin stage and no host write of constraint_penalty since the last reset)");
     return solve_launch(h, 1);
 }
 
@@ -969,9 +1039,8 @@ static int policy_check(const ilqr_handle* h, int32_t samples, const double* x1,
     if (!cost) return fail(ILQR_ERR_INVALID, me + ": null cost");
     if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
     if (w && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w given, but this model has no parameters (num_parameter == 0)");
-    bool pol = h->has_policy;
-    if (!h->shards.empty()) { pol = true; for (const ilqr_handle* s : h->shards) pol = pol && s->has_policy; }
-    if (!pol) return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
+    if (!every_shard_holds(h, &ilqr_handle::has_policy))
+        return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
     return ILQR_OK;
 }
 
@@ -980,7 +1049,7 @@ static int policy_launch(ilqr_handle* h, int32_t samples, double step_size, cons
     if (!h->vt->launch_policy_rollout) return fail(ILQR_ERR_MODEL, "this model module has no policy rollout kernel");
     ilqr::PolicyArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = samples; a.constrained = h->constrained; a.n_sel = h->n_sel;
-    a.waves = (samples + 63) / 64 > 4 ? 4 : (samples + 63) / 64;
+    a.waves = waves_for(samples);
     a.alpha = step_size; a.x1 = x1; a.w = w; a.cost = cost; a.viol = max_violation; a.nonfinite = first_nonfinite; a.x = x; a.u = u;
     if (h->vt->launch_policy_rollout(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "policy rollout launch failed");
     return ILQR_OK;
@@ -988,46 +1057,34 @@ static int policy_launch(ilqr_handle* h, int32_t samples, double step_size, cons
 
 int ilqr_rollout_policy_device(ilqr_handle* h, int32_t samples, double step_size, const double* x1, const double* w, double* cost,
                                double* max_violation, int32_t* first_nonfinite, double* x, double* u) {
-    const int rc = policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy_device");
-    if (rc != ILQR_OK) return rc;
-    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_rollout_policy (host pointers) on a sharded handle");
+    ILQR_TRY(policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_rollout_policy");
     HIP_TRY(hipSetDevice(h->device));
     return policy_launch(h, samples, step_size, x1, w, cost, max_violation, first_nonfinite, x, u);
 }
 
 int ilqr_rollout_policy(ilqr_handle* h, int32_t samples, double step_size, const double* x1, const double* w, double* cost,
                         double* max_violation, int32_t* first_nonfinite, double* x, double* u) {
-    int rc = policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy");
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy"));
     const size_t S = (size_t)samples, T = (size_t)h->L.T, N = T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         const size_t o = lo * S;
-        return ilqr_rollout_policy(s, samples, step_size, x1 + o * n, w ? w + o * T * nwu : nullptr, cost + o, max_violation ? max_violation + o : nullptr,
-                                   first_nonfinite ? first_nonfinite + o : nullptr, x ? x + o * T * n : nullptr, u ? u + o * N * m : nullptr); }, true);
+        return ilqr_rollout_policy(s, samples, step_size, x1 + o * n, at(w, o * T * nwu), cost + o, at(max_violation, o), at(first_nonfinite, o),
+                                   at(x, o * T * n), at(u, o * N * m)); }, true);
     HIP_TRY(hipSetDevice(h->device));
     const size_t BS = (size_t)h->B * S;
-    const size_t bytes[7] = {BS * n * 8, w ? BS * T * nwu * 8 : 0, BS * 8, max_violation ? BS * 8 : 0, first_nonfinite ? BS * 4 : 0,
-                             x ? BS * T * n * 8 : 0, u ? BS * N * m * 8 : 0};
-    void* d[7];
-    for (int i = 0; i < 7; ++i) {
-        ilqr_handle::Stage& st = h->pol[i];
-        if (bytes[i] > st.cap) {
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            if (st.p) { HIP_TRY(hipFree(st.p)); st.p = nullptr; st.cap = 0; }
-            HIP_TRY(hipMalloc(&st.p, bytes[i]));
-            st.cap = bytes[i];
-        }
-        d[i] = bytes[i] ? st.p : nullptr;
-    }
-    HIP_TRY(hipMemcpyAsync(d[0], x1, bytes[0], hipMemcpyHostToDevice, h->stream));
-    if (w) HIP_TRY(hipMemcpyAsync(d[1], w, bytes[1], hipMemcpyHostToDevice, h->stream));
-    rc = policy_launch(h, samples, step_size, (const double*)d[0], (const double*)d[1], (double*)d[2], (double*)d[3], (int32_t*)d[4], (double*)d[5], (double*)d[6]);
-    if (rc != ILQR_OK) return rc;
-    void* host[7] = {nullptr, nullptr, cost, max_violation, first_nonfinite, x, u};
-    for (int i = 2; i < 7; ++i)
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ILQR_OK;
+    const Staged s_x1 = staged_in(h->pol[POL_X1], x1, BS * n * 8);
+    const Staged s_w = staged_in(h->pol[POL_W], w, BS * T * nwu * 8);
+    const Staged s_cost = staged_out(h->pol[POL_COST], cost, BS * 8);
+    const Staged s_viol = staged_out(h->pol[POL_VIOL], max_violation, BS * 8);
+    const Staged s_nonfinite = staged_out(h->pol[POL_NONFINITE], first_nonfinite, BS * 4);
+    const Staged s_x = staged_out(h->pol[POL_X], x, BS * T * n * 8);
+    const Staged s_u = staged_out(h->pol[POL_U], u, BS * N * m * 8);
+    const auto arrays = {s_x1, s_w, s_cost, s_viol, s_nonfinite, s_x, s_u};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(policy_launch(h, samples, step_size, s_x1.dev<const double>(), s_w.dev<const double>(), s_cost.dev<double>(), s_viol.dev<double>(),
+                           s_nonfinite.dev<int32_t>(), s_x.dev<double>(), s_u.dev<double>()));
+    return stage_out(h, arrays);
 }
 
 // ---- scoring and selection of candidate initial guesses (ilqr_device_candidates.hpp), then the existing init_rollout on the winners
@@ -1042,80 +1099,55 @@ static int candidates_check(const ilqr_handle* h, int32_t candidates, double vio
     return ILQR_OK;
 }
 
-static int grow(ilqr_handle* h, ilqr_handle::Stage& st, size_t bytes) {
-    if (bytes <= st.cap) return ILQR_OK;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (st.p) { HIP_TRY(hipFree(st.p)); st.p = nullptr; st.cap = 0; }
-    HIP_TRY(hipMalloc(&st.p, bytes));
-    st.cap = bytes;
-    return ILQR_OK;
-}
-
 // every pointer a device pointer on h's device; x1 may be h->d_x1 itself. Null outputs are replaced by the handle's own buffers.
 static int candidates_launch(ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u, int32_t* chosen,
                              double* cost, double* max_violation, int32_t* first_nonfinite) {
     if (!h->vt->launch_candidates) return fail(ILQR_ERR_MODEL, "this model module has no candidate scoring kernel");
     const size_t BS = (size_t)h->B * (size_t)candidates;
-    if (!cost) { const int rc = grow(h, h->cand[1], BS * 8); if (rc != ILQR_OK) return rc; cost = (double*)h->cand[1].p; }
-    if (!max_violation) { const int rc = grow(h, h->cand[2], BS * 8); if (rc != ILQR_OK) return rc; max_violation = (double*)h->cand[2].p; }
-    if (!first_nonfinite) { const int rc = grow(h, h->cand[3], BS * 4); if (rc != ILQR_OK) return rc; first_nonfinite = (int32_t*)h->cand[3].p; }
+    ILQR_TRY(own_if_null(h, cost, h->cand[CAND_COST], BS * 8));
+    ILQR_TRY(own_if_null(h, max_violation, h->cand[CAND_VIOL], BS * 8));
+    ILQR_TRY(own_if_null(h, first_nonfinite, h->cand[CAND_NONFINITE], BS * 4));
     ilqr::CandArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = candidates; a.constrained = h->constrained;
-    a.waves = (candidates + 63) / 64 > 4 ? 4 : (candidates + 63) / 64;
+    a.waves = waves_for(candidates);
     a.weight = violation_weight; a.x1 = x1; a.u = u; a.cost = cost; a.viol = max_violation; a.nonfinite = first_nonfinite; a.chosen = chosen;
     a.r_x1 = h->d_x1; a.r_u = h->d_u;
     if (h->vt->launch_candidates(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "candidate scoring launch failed");
     return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);       // the code that defines the installed state
 }
 
-static int resident_inputs(ilqr_handle* h) {
-    const size_t bx = (size_t)h->B * h->vt->nx * 8, bu = (size_t)h->B * (h->L.T - 1) * h->vt->nu * 8;
-    if (!h->d_x1) HIP_TRY(hipMalloc((void**)&h->d_x1, bx));
-    if (!h->d_u) HIP_TRY(hipMalloc((void**)&h->d_u, bu));
-    return ILQR_OK;
-}
-
 int ilqr_initialize_rollout_candidates_device(ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u,
                                               int32_t* chosen, double* cost, double* max_violation, int32_t* first_nonfinite) {
-    int rc = candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates_device");
-    if (rc != ILQR_OK) return rc;
-    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_initialize_rollout_candidates (host pointers) on a sharded handle");
+    ILQR_TRY(candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_initialize_rollout_candidates");
     HIP_TRY(hipSetDevice(h->device));
-    rc = resident_inputs(h);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(resident_inputs(h));
     return candidates_launch(h, candidates, violation_weight, x1, u, chosen, cost, max_violation, first_nonfinite);
 }
 
 int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, double violation_weight, const double* x1, const double* u,
                                        int32_t* chosen, double* cost, double* max_violation, int32_t* first_nonfinite) {
-    int rc = candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates");
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates"));
     const size_t S = (size_t)candidates, N = (size_t)h->L.T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu;
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         const size_t o = lo * S;
-        return ilqr_initialize_rollout_candidates(s, candidates, violation_weight, x1 + lo * n, u + o * N * m, chosen ? chosen + lo : nullptr,
-                                                  cost ? cost + o : nullptr, max_violation ? max_violation + o : nullptr,
-                                                  first_nonfinite ? first_nonfinite + o : nullptr); }, true);
+        return ilqr_initialize_rollout_candidates(s, candidates, violation_weight, x1 + lo * n, u + o * N * m, at(chosen, lo), at(cost, o),
+                                                  at(max_violation, o), at(first_nonfinite, o)); }, true);
     HIP_TRY(hipSetDevice(h->device));
-    rc = resident_inputs(h);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(resident_inputs(h));
     const size_t B = (size_t)h->B, BS = B * S;
-    const size_t bytes[5] = {BS * N * m * 8, cost ? BS * 8 : 0, max_violation ? BS * 8 : 0, first_nonfinite ? BS * 4 : 0, chosen ? B * 4 : 0};
-    void* d[5];
-    for (int i = 0; i < 5; ++i) {
-        rc = grow(h, h->cand[i], bytes[i]);
-        if (rc != ILQR_OK) return rc;
-        d[i] = bytes[i] ? h->cand[i].p : nullptr;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_x1, x1, B * n * 8, hipMemcpyHostToDevice, h->stream));
-    if (bytes[0]) HIP_TRY(hipMemcpyAsync(d[0], u, bytes[0], hipMemcpyHostToDevice, h->stream));
-    rc = candidates_launch(h, candidates, violation_weight, h->d_x1, bytes[0] ? (const double*)d[0] : h->d_u, (int32_t*)d[4], (double*)d[1], (double*)d[2], (int32_t*)d[3]);
-    if (rc != ILQR_OK) return rc;
-    void* host[5] = {nullptr, cost, max_violation, first_nonfinite, chosen};
-    for (int i = 1; i < 5; ++i)
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ILQR_OK;
+    ilqr_handle::Stage resident_x1{h->d_x1, B * n * 8};     // x1 goes straight into the resident input: a stage that never grows
+    const Staged s_x1 = staged_in(resident_x1, x1, B * n * 8);
+    const Staged s_u = staged_in(h->cand[CAND_U], u, BS * N * m * 8);        // (N == 0: no actions to stage; the launch gets d_u instead)
+    const Staged s_cost = staged_out(h->cand[CAND_COST], cost, BS * 8);
+    const Staged s_viol = staged_out(h->cand[CAND_VIOL], max_violation, BS * 8);
+    const Staged s_nonfinite = staged_out(h->cand[CAND_NONFINITE], first_nonfinite, BS * 4);
+    const Staged s_chosen = staged_out(h->cand[CAND_CHOSEN], chosen, B * 4);
+    const auto arrays = {s_x1, s_u, s_cost, s_viol, s_nonfinite, s_chosen};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(candidates_launch(h, candidates, violation_weight, h->d_x1, s_u.bytes ? s_u.dev<const double>() : h->d_u, s_chosen.dev<int32_t>(),
+                               s_cost.dev<double>(), s_viol.dev<double>(), s_nonfinite.dev<int32_t>()));
+    return stage_out(h, arrays);
 }
 
 // ---- candidates drawn on the device around a base sequence (ilqr_device_sample.hpp), then the existing init_rollout on what was installed
@@ -1136,9 +1168,7 @@ static int sample_check(const ilqr_handle* h, int32_t candidates, int32_t mode, 
         if (!(sigma[j] >= 0.0) || !std::isfinite(sigma[j])) return fail(ILQR_ERR_INVALID, me + ": sigma must be finite and >= 0");
     if (h->L.T - 1 > ilqr::SAMPLE_MAX_STEPS) return fail(ILQR_ERR_INVALID, me + ": more than 2^20 steps");
     if (first_instance + (int64_t)h->B > ilqr::SAMPLE_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance + batch must not exceed 2^23");
-    bool rx = h->d_x1 != nullptr, ru = h->d_u != nullptr;
-    if (!h->shards.empty()) { rx = ru = true; for (const ilqr_handle* s : h->shards) { rx = rx && s->d_x1; ru = ru && s->d_u; } }
-    if ((!x1 && !rx) || (!base_u && !ru))
+    if ((!x1 && !every_shard_holds(h, &ilqr_handle::d_x1)) || (!base_u && !every_shard_holds(h, &ilqr_handle::d_u)))
         return fail(ILQR_ERR_INVALID, me + ": NULL x1 / base_u mean the handle's resident inputs, and it holds none yet (no initialize_rollout or shift has run)");
     return ILQR_OK;
 }
@@ -1149,24 +1179,21 @@ static int sample_launch(ilqr_handle* h, int32_t candidates, int32_t mode, uint6
                          double violation_weight, double temperature, const double* x1, const double* base_u, int32_t* chosen, double* cost,
                          double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
     if (!h->vt->launch_sample_candidates) return fail(ILQR_ERR_MODEL, "this model module has no candidate sampling kernel");
-    int rc = resident_inputs(h);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(resident_inputs(h));
     const size_t BS = (size_t)h->B * (size_t)candidates, nu = (size_t)h->L.nu;
-    if (!cost) { rc = grow(h, h->cand[1], BS * 8); if (rc != ILQR_OK) return rc; cost = (double*)h->cand[1].p; }
-    if (!max_violation) { rc = grow(h, h->cand[2], BS * 8); if (rc != ILQR_OK) return rc; max_violation = (double*)h->cand[2].p; }
-    if (!first_nonfinite) { rc = grow(h, h->cand[3], BS * 4); if (rc != ILQR_OK) return rc; first_nonfinite = (int32_t*)h->cand[3].p; }
-    if (!chosen) { rc = grow(h, h->cand[4], (size_t)h->B * 4); if (rc != ILQR_OK) return rc; chosen = (int32_t*)h->cand[4].p; }
-    if (!weights && mode == ILQR_SAMPLE_BLEND) { rc = grow(h, h->samp[0], BS * 8); if (rc != ILQR_OK) return rc; weights = (double*)h->samp[0].p; }
-    rc = grow(h, h->samp[2], nu * 8);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(own_if_null(h, cost, h->cand[CAND_COST], BS * 8));
+    ILQR_TRY(own_if_null(h, max_violation, h->cand[CAND_VIOL], BS * 8));
+    ILQR_TRY(own_if_null(h, first_nonfinite, h->cand[CAND_NONFINITE], BS * 4));
+    ILQR_TRY(own_if_null(h, chosen, h->cand[CAND_CHOSEN], (size_t)h->B * 4));
+    if (mode == ILQR_SAMPLE_BLEND) ILQR_TRY(own_if_null(h, weights, h->samp[SAMP_WEIGHTS], BS * 8));
     h->sample_sigma.assign(sigma, sigma + nu);        // the caller's array may go away before the (asynchronous) copy has read it
-    HIP_TRY(hipMemcpyAsync(h->samp[2].p, h->sample_sigma.data(), nu * 8, hipMemcpyHostToDevice, h->stream));
+    ILQR_TRY(stage_in(h, {staged_in(h->samp[SAMP_SIGMA], h->sample_sigma.data(), nu * 8)}));
     ilqr::SampleArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = candidates; a.constrained = h->constrained;
-    a.waves = (candidates + 63) / 64 > 4 ? 4 : (candidates + 63) / 64;
+    a.waves = waves_for(candidates);
     a.weight = violation_weight; a.x1 = x1 ? x1 : h->d_x1; a.u = nullptr; a.cost = cost; a.viol = max_violation; a.nonfinite = first_nonfinite; a.chosen = chosen;
     a.r_x1 = h->d_x1; a.r_u = h->d_u;
-    a.seed = seed; a.b0 = first_instance; a.sigma = (const double*)h->samp[2].p; a.base = base_u ? base_u : h->d_u; a.u_out = u_out; a.weights = weights;
+    a.seed = seed; a.b0 = first_instance; a.sigma = (const double*)h->samp[SAMP_SIGMA].p; a.base = base_u ? base_u : h->d_u; a.u_out = u_out; a.weights = weights;
     a.mode = mode; a.temperature = temperature;
     if (h->vt->launch_sample_candidates(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "candidate sampling launch failed");
     return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);       // the code that defines the installed state
@@ -1175,9 +1202,8 @@ static int sample_launch(ilqr_handle* h, int32_t candidates, int32_t mode, uint6
 int ilqr_sample_rollout_candidates_device(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance, const double* sigma,
                                           double violation_weight, double temperature, const double* x1, const double* base_u, int32_t* chosen,
                                           double* cost, double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
-    const int rc = sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates_device");
-    if (rc != ILQR_OK) return rc;
-    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_sample_rollout_candidates (host pointers) on a sharded handle");
+    ILQR_TRY(sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_sample_rollout_candidates");
     HIP_TRY(hipSetDevice(h->device));
     return sample_launch(h, candidates, mode, seed, first_instance, sigma, violation_weight, temperature, x1, base_u, chosen, cost, max_violation,
                          first_nonfinite, weights, u_out);
@@ -1186,40 +1212,30 @@ int ilqr_sample_rollout_candidates_device(ilqr_handle* h, int32_t candidates, in
 int ilqr_sample_rollout_candidates(ilqr_handle* h, int32_t candidates, int32_t mode, uint64_t seed, int64_t first_instance, const double* sigma,
                                    double violation_weight, double temperature, const double* x1, const double* base_u, int32_t* chosen,
                                    double* cost, double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
-    int rc = sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates");
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates"));
     const size_t S = (size_t)candidates, N = (size_t)h->L.T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu;
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         const size_t o = lo * S;
         return ilqr_sample_rollout_candidates(s, candidates, mode, seed, first_instance + (int64_t)lo, sigma, violation_weight, temperature,
-                                              x1 ? x1 + lo * n : nullptr, base_u ? base_u + lo * N * m : nullptr, chosen ? chosen + lo : nullptr,
-                                              cost ? cost + o : nullptr, max_violation ? max_violation + o : nullptr,
-                                              first_nonfinite ? first_nonfinite + o : nullptr, weights ? weights + o : nullptr,
-                                              u_out ? u_out + o * N * m : nullptr); }, true);
+                                              at(x1, lo * n), at(base_u, lo * N * m), at(chosen, lo), at(cost, o), at(max_violation, o),
+                                              at(first_nonfinite, o), at(weights, o), at(u_out, o * N * m)); }, true);
     HIP_TRY(hipSetDevice(h->device));
-    rc = resident_inputs(h);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(resident_inputs(h));
     const size_t B = (size_t)h->B, BS = B * S;
-    const size_t bytes[6] = {cost ? BS * 8 : 0, max_violation ? BS * 8 : 0, first_nonfinite ? BS * 4 : 0, chosen ? B * 4 : 0, weights ? BS * 8 : 0,
-                             u_out ? BS * N * m * 8 : 0};
-    ilqr_handle::Stage* st[6] = {&h->cand[1], &h->cand[2], &h->cand[3], &h->cand[4], &h->samp[0], &h->samp[1]};
-    void* d[6];
-    for (int i = 0; i < 6; ++i) {
-        rc = grow(h, *st[i], bytes[i]);
-        if (rc != ILQR_OK) return rc;
-        d[i] = bytes[i] ? st[i]->p : nullptr;
-    }
+    const Staged s_cost = staged_out(h->cand[CAND_COST], cost, BS * 8);
+    const Staged s_viol = staged_out(h->cand[CAND_VIOL], max_violation, BS * 8);
+    const Staged s_nonfinite = staged_out(h->cand[CAND_NONFINITE], first_nonfinite, BS * 4);
+    const Staged s_chosen = staged_out(h->cand[CAND_CHOSEN], chosen, B * 4);
+    const Staged s_weights = staged_out(h->samp[SAMP_WEIGHTS], weights, BS * 8);
+    const Staged s_u_out = staged_out(h->samp[SAMP_U_OUT], u_out, BS * N * m * 8);
+    const auto arrays = {s_cost, s_viol, s_nonfinite, s_chosen, s_weights, s_u_out};
+    ILQR_TRY(stage_in(h, arrays));
     // the caller's x1 and base go straight into the resident inputs: the installation works in place
     if (x1) HIP_TRY(hipMemcpyAsync(h->d_x1, x1, B * n * 8, hipMemcpyHostToDevice, h->stream));
     if (base_u) HIP_TRY(hipMemcpyAsync(h->d_u, base_u, B * N * m * 8, hipMemcpyHostToDevice, h->stream));
-    rc = sample_launch(h, candidates, mode, seed, first_instance, sigma, violation_weight, temperature, h->d_x1, h->d_u, (int32_t*)d[3], (double*)d[0],
-                       (double*)d[1], (int32_t*)d[2], (double*)d[4], (double*)d[5]);
-    if (rc != ILQR_OK) return rc;
-    void* host[6] = {cost, max_violation, first_nonfinite, chosen, weights, u_out};
-    for (int i = 0; i < 6; ++i)
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(host[i], d[i], bytes[i], hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ILQR_OK;
+    ILQR_TRY(sample_launch(h, candidates, mode, seed, first_instance, sigma, violation_weight, temperature, h->d_x1, h->d_u, s_chosen.dev<int32_t>(),
+                           s_cost.dev<double>(), s_viol.dev<double>(), s_nonfinite.dev<int32_t>(), s_weights.dev<double>(), s_u_out.dev<double>()));
+    return stage_out(h, arrays);
 }
 
 // ---- receding-horizon shift (ilqr_device_shift.hpp), then the existing init_rollout on the shifted inputs
@@ -1234,59 +1250,45 @@ static int shift_check(const ilqr_handle* h, int32_t steps, int32_t tail, int32_
     if (w_tail && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_tail given, but this model has no parameters (num_parameter == 0)");
     if (steps > 0 && h->n_sel > 0)
         return fail(ILQR_ERR_INVALID, me + ": the handle has stage selectors attached: the structure of a lowered problem belongs to horizon positions and cannot be shifted");
-    if (feedback) {
-        bool pol = h->has_policy;
-        if (!h->shards.empty()) { pol = true; for (const ilqr_handle* s : h->shards) pol = pol && s->has_policy; }
-        if (!pol) return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
-    }
+    if (feedback && !every_shard_holds(h, &ilqr_handle::has_policy))
+        return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
     return ILQR_OK;
 }
 
 // x1, w_tail: null or device pointers on h's device
 static int shift_launch(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
     if (!h->vt->launch_shift) return fail(ILQR_ERR_MODEL, "this model module has no horizon shift kernel");
-    int rc = resident_inputs(h);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(resident_inputs(h));
     ilqr::ShiftArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.tail = tail; a.feedback = feedback ? 1 : 0; a.phase = 0;
     a.x1 = x1; a.w_tail = w_tail; a.w_stage = nullptr; a.r_x1 = h->d_x1; a.r_u = h->d_u;
     if (steps > 0 && h->L.nw > 0) {            // (no selectors here: every parameter column is the user's)
-        rc = grow(h, h->shift[2], (size_t)h->B * h->L.T * h->L.nw * 8);
-        if (rc != ILQR_OK) return rc;
-        a.w_stage = (double*)h->shift[2].p;
+        ILQR_TRY(grow(h, h->shift[SHIFT_W_STAGE], (size_t)h->B * h->L.T * h->L.nw * 8));
+        a.w_stage = (double*)h->shift[SHIFT_W_STAGE].p;
     }
     if (h->vt->launch_shift(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "horizon shift launch failed");
     return ilqr_initialize_rollout_device(h, h->d_x1, h->d_u);       // the code that defines the installed state
 }
 
 int ilqr_shift_horizon_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
-    const int rc = shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon_device");
-    if (rc != ILQR_OK) return rc;
-    if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "device pointers belong to one device: call ilqr_shift_horizon (host pointers) on a sharded handle");
+    ILQR_TRY(shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_shift_horizon");
     HIP_TRY(hipSetDevice(h->device));
     return shift_launch(h, steps, tail, feedback, x1, w_tail);
 }
 
 int ilqr_shift_horizon(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
-    int rc = shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon");
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon"));
     const size_t n = (size_t)h->L.nx, kw = (size_t)steps * (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_shift_horizon(s, steps, tail, feedback, x1 ? x1 + lo * n : nullptr, w_tail ? w_tail + lo * kw : nullptr); }, true);
+        return ilqr_shift_horizon(s, steps, tail, feedback, at(x1, lo * n), at(w_tail, lo * kw)); }, true);
     HIP_TRY(hipSetDevice(h->device));
-    const size_t bytes[2] = {x1 ? (size_t)h->B * n * 8 : 0, w_tail ? (size_t)h->B * kw * 8 : 0};
-    const double* host[2] = {x1, w_tail};
-    const double* d[2];
-    for (int i = 0; i < 2; ++i) {
-        rc = grow(h, h->shift[i], bytes[i]);
-        if (rc != ILQR_OK) return rc;
-        d[i] = bytes[i] ? (const double*)h->shift[i].p : nullptr;
-        if (bytes[i]) HIP_TRY(hipMemcpyAsync(h->shift[i].p, host[i], bytes[i], hipMemcpyHostToDevice, h->stream));
-    }
-    rc = shift_launch(h, steps, tail, feedback, d[0], d[1]);
-    if (rc != ILQR_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));   // host buffers may be reused by the caller
-    return ILQR_OK;
+    const Staged s_x1 = staged_in(h->shift[SHIFT_X1], x1, (size_t)h->B * n * 8);
+    const Staged s_w_tail = staged_in(h->shift[SHIFT_W_TAIL], w_tail, (size_t)h->B * kw * 8);
+    const auto arrays = {s_x1, s_w_tail};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(shift_launch(h, steps, tail, feedback, s_x1.dev<const double>(), s_w_tail.dev<const double>()));
+    return stage_out(h, arrays);               // (inputs only: the synchronise, after which the caller may reuse its host arrays)
 }
 
 // ---- receding-horizon shift of the duals and penalties (ilqr_device_duals.hpp)
@@ -1300,13 +1302,12 @@ static int duals_check(const ilqr_handle* h, int32_t steps, int32_t tail, int32_
     if (penalty != ILQR_DUALS_PENALTY_KEEP && penalty != ILQR_DUALS_PENALTY_RESET) return fail(ILQR_ERR_INVALID, me + ": unknown penalty mode");
     if (steps > 0 && h->n_sel > 0)
         return fail(ILQR_ERR_INVALID, me + ": the handle has stage selectors attached: the structure of a lowered problem belongs to horizon positions and cannot be shifted");
-    if (!holds_duals(h)) return fail(ILQR_ERR_INVALID, me + ": the handle holds no duals yet (no constrained solve, no al_begin stage and no host write of constraint_penalty since the last reset)");
+    if (!every_shard_holds(h, &ilqr_handle::has_duals)) return fail(ILQR_ERR_INVALID, me + ": the handle holds no duals yet (no constrained solve, no al_begin stage and no host write of constraint_penalty since the last reset)");
     return ILQR_OK;
 }
 
 int ilqr_shift_duals_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty) {
-    const int rc = duals_check(h, steps, tail, penalty, "ilqr_shift_duals_device");
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(duals_check(h, steps, tail, penalty, "ilqr_shift_duals_device"));
     if (SHARDED(h)) return fail(ILQR_ERR_INVALID, "ilqr_shift_duals_device: a sharded handle has one stream per device: call ilqr_shift_duals on it");
     if (!h->vt->launch_shift_duals) return fail(ILQR_ERR_MODEL, "this model module has no dual shift kernel");
     HIP_TRY(hipSetDevice(h->device));
@@ -1317,11 +1318,9 @@ int ilqr_shift_duals_device(ilqr_handle* h, int32_t steps, int32_t tail, int32_t
 }
 
 int ilqr_shift_duals(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalty) {
-    int rc = duals_check(h, steps, tail, penalty, "ilqr_shift_duals");
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(duals_check(h, steps, tail, penalty, "ilqr_shift_duals"));
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t) { return ilqr_shift_duals(s, steps, tail, penalty); });
-    rc = ilqr_shift_duals_device(h, steps, tail, penalty);
-    if (rc != ILQR_OK) return rc;
+    ILQR_TRY(ilqr_shift_duals_device(h, steps, tail, penalty));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
 }
