@@ -8,6 +8,7 @@ Julia closure, a C++ struct of `__device__` functions is emitted that the
 solve kernels (csrc/ilqr_device.hpp) are instantiated with.
 """
 import hashlib
+import threading
 
 import sympy as sp
 from sympy.printing.c import C99CodePrinter
@@ -673,7 +674,16 @@ def _emit_compact_hessians(L, add, add_al_c, al_terms, cost_stage, cost_term, co
              con_term if nct else dynamics, compact(al_t_o), al_t_unp, False)
 
 
+_GENERATE_LOCK = threading.Lock()      # the emitters below keep their context in module globals (COOP_GROUP, _CTX, _CONST_CTX)
+
+
 def generate_model_source(name, dynamics, cost_stage, cost_term, con_stage=None, con_term=None):
+    """generate_model_source, one call at a time: callers may compile several models from a pool of threads."""
+    with _GENERATE_LOCK:
+        return _generate_model_source(name, dynamics, cost_stage, cost_term, con_stage, con_term)
+
+
+def _generate_model_source(name, dynamics, cost_stage, cost_term, con_stage=None, con_term=None):
     """Return (struct_name, C++ source) of the device model struct.
 
     dynamics: Dynamics; cost_stage/cost_term: Cost (terminal has num_action == 0);

@@ -1,6 +1,8 @@
 // Host-side check of the model compiler (iterativelqr.jl_amd/csrc/ilqr_model_compile.cpp); built together with it and run by
 // tests/test_model_compile_host.py: no hipcc, no libilqr_hip.so, no GPU. argv: the C source of synth12, a scratch directory.
 // Prints one line per check and exits non-zero on the first that fails.
+// Second form, run by tests/test_coupled_problem.py: --probe, a scratch directory, then pairs of files — the C callables of a model
+// and the compact Hessian row expected of the probe ("nx nu nc_stage", "nxx nuu nux", the indices, the tile starts).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -41,7 +43,38 @@ static std::vector<fs::path> bins(const std::string& dir) {
     return v;
 }
 
+static std::vector<int> ints(const std::string& line) {
+    std::vector<int> v;
+    std::stringstream s(line);
+    for (int e; s >> e;) v.push_back(e);
+    return v;
+}
+
+// the probe on models whose Hessians are coupled: gux entries, off-diagonal gxx / guu entries, several gxx tiles
+static int probe_given_models(int argc, char** argv) {
+    const std::string dir = argv[2];
+    for (int a = 3; a + 1 < argc; a += 2) {
+        std::stringstream text;
+        text << std::ifstream(argv[a]).rdbuf();
+        const std::string source = text.str();
+        std::ifstream expect(argv[a + 1]);
+        std::string l0, l1, l2, l3;
+        std::getline(expect, l0); std::getline(expect, l1); std::getline(expect, l2); std::getline(expect, l3);
+        const std::vector<int> dims = ints(l0), sizes = ints(l1), idx = ints(l2), starts = ints(l3);
+        CHECK(dims.size() == 3 && sizes.size() == 3 && (int)idx.size() == sizes[0] + sizes[1] + sizes[2]);
+        ilqr_model_source src = {"coupled_host", dims[0], dims[1], 0, dims[2], 0, (1ull << dims[2]) - 1, 0, source.c_str(), 0};
+        const ModelStructure ms = probe_model_structure(&src, dir, "coupled", ProbeHints());
+        CHECK(ms.found);
+        CHECK(ms.nxx == sizes[0] && ms.nuu == sizes[1] && ms.nux == sizes[2] && ms.nux > 0);
+        CHECK(ms.hess_idx == idx);
+        CHECK(ms.tile_start == starts);
+    }
+    std::printf("%d checks passed\n", checks);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 5 && std::strcmp(argv[1], "--probe") == 0) return probe_given_models(argc, argv);
     if (argc != 3) return 2;
     std::stringstream text;
     text << std::ifstream(argv[1]).rdbuf();

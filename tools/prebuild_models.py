@@ -25,6 +25,14 @@ def main(verbose=True):
         (b"synth64_c", (64, 16, 0, 32, 0, (1 << 32) - 1, 0), pkg.models.synth_c_source(64, 16).encode(), False),
         (b"synth12_t", (12, 5, 0, 10, 3, (1 << 10) - 1, 0), ex("synth12_model.c"), True),
     ]
+    # the coupled-Hessian family of tests/coupled_problem.py: (12, 5) as C callables here, every size through the symbolic generator
+    # below. The family is the tests' own: a tree without that file builds everything else, and the tests compile on demand
+    CP = None
+    if os.path.exists(os.path.join(ROOT, "tests", "coupled_problem.py")):
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import coupled_problem as CP
+        for probe in (True, False):
+            jobs.append((b"coupled12_c", (12, 5, 0, 12, 0, (1 << 12) - 1, 0), CP.c_source(pkg, 12, 5).encode(), probe))
     old = os.environ.get("ILQR_NO_STRUCTURE_PROBE")
     try:
         for name, dims, text, probe in jobs:
@@ -50,6 +58,17 @@ def main(verbose=True):
                 raise RuntimeError("ilqr_compile_model_stages(%s): %s" % (name.decode(), L.ilqr_last_error().decode()[-600:]))
             if verbose:
                 print("model module %s (per-step kinds): %s" % (reg.value.decode(), os.path.basename(path.value.decode())))
+        # symbolic models (api.compile_model, as Solver(dynamics, costs, constraints) does): hipcc children, a few at a time
+        from concurrent.futures import ThreadPoolExecutor
+        lowered = []
+        for n, m, T, con in sorted(set((n, m, 11, con) for n, m, _, con in (CP.CASES if CP else []))):       # (the horizon does not enter the module)
+            dyn, costs, cons, name = CP.product_problem(pkg, n, m, T, con)
+            low = pkg.lowering.lower(dyn, costs, cons)
+            lowered.append((name, low["dynamics"], low["cost_stage"], low["cost_term"], low["con_stage"], low["con_term"]))
+        with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:
+            for reg, path in pool.map(lambda job: pkg.api.compile_model(*job), lowered):
+                if verbose:
+                    print("model module %s (symbolic): %s" % (reg, os.path.basename(path)))
     finally:
         if old is None:
             os.environ.pop("ILQR_NO_STRUCTURE_PROBE", None)
