@@ -254,6 +254,70 @@ int ilqr_solve(ilqr_handle* h);
 int ilqr_solve_warm(ilqr_handle* h);
 int ilqr_synchronize(ilqr_handle* h);
 
+/* The plant of a closed MPC loop, on the device: every instance's plant state x[b] is advanced by k = `steps` control periods under
+ * the head of the handle's plan, horizon positions 0 .. k−1 of x̄, ū, K, θ as the handle holds them when the call is made. For
+ * i = 0 .. k−1, with g = step0 + i the global plant step:
+ *     u_i = ū_i (feedback == 0), else ū_i + K_i (x − x̄_i)   (src/rollout.jl:24-28 as ilqr_rollout_policy forms it with step_size = 0:
+ *                                                            (ū + K x) − K x̄)
+ *     w_i = the user's columns of w_plant[b][i] if given (a plant / model mismatch), else of θ_i; the selector columns of a lowered
+ *           problem are always θ_i's
+ *     x ← f(x, u_i, w_i), then x_j ← x_j + sigma_x[j] · z(seed, first_instance + b, 1 + j / 16, g, j % 16) for every component j
+ *           with sigma_x[j] != 0 (product and sum rounded separately)
+ * z is the z of ilqr_sample_rollout_candidates, its candidate field carrying the state component's high bits offset by one:
+ * ilqr_candidate_noise(seed, first_instance, B, 1 + ceil(nx / 16), step0 + k, 16, z) is the host twin (its row 0 is zero by
+ * contract; the offset keeps every drawn component out of it). x_out: the plant states, row 0 the input state; u_out: the actions
+ * applied; first_nonfinite: −1, or the first i with a non-finite component of the state after step i. The call READS the handle, as
+ * ilqr_rollout_policy does: workspace, scalars, trace, timing and resident inputs are untouched. Refused (ILQR_ERR_INVALID) without
+ * touching the GPU: a null handle or x, steps < 1 or > T−1, step0 < 0 or step0 + steps > 2^20, first_instance < 0 or first_instance
+ * + batch > 2^23, a negative or non-finite sigma_x entry, nx > 64, w_plant on a model without user parameters, feedback without a
+ * policy (the rule of ilqr_rollout_policy). Host form: stages through device buffers the handle owns and reuses, works on a
+ * sharded handle (b counts over the whole batch), synchronous. Device form: every pointer but sigma_x a device pointer on the
+ * handle's device, asynchronous on the handle's stream; refused on a sharded handle. */
+int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                    const double* sigma_x,     /* HOST, NULL or [nx], finite, >= 0 */
+                    const double* w_plant,     /* NULL, or [B][steps][nw_user] */
+                    double* x,                 /* [B][nx], in: plant state, out: plant state after k steps */
+                    double* x_out,             /* NULL, or [B][steps+1][nx]  (row 0 = the input state) */
+                    double* u_out,             /* NULL, or [B][steps][nu]    (the actions applied) */
+                    int32_t* first_nonfinite); /* NULL, or [B] */
+int ilqr_plant_step_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                           const double* sigma_x, const double* d_w_plant, double* d_x, double* d_x_out, double* d_u_out,
+                           int32_t* d_first_nonfinite);
+
+/* The closed MPC loop of B controllers over P = periods re-solves, enqueued once and synchronised once. From the plant state x0[b]
+ * (NULL: x̄_0 of the handle) the call runs for p = 0 .. P−1, with k = steps, on a plant state that stays on the device:
+ *   1. ilqr_plant_step_device(k, plant_feedback, seed, first_instance, step0 = p·k, sigma_x, w_plant rows p·k .., ...)
+ *   2. ilqr_shift_horizon_device(k, shift_tail, shift_feedback, x1 = the plant state, NULL)
+ *   3. warm: ilqr_shift_duals_device(k, duals_tail, duals_penalty)
+ *   4. warm: ilqr_solve_warm, else ilqr_solve
+ *   5. row p of the log: the nine scalars of ilqr_stats of every instance, as doubles, in ilqr_stats order
+ * and leaves the handle in exactly the state that sequence of calls leaves it in. x_cl: the plant states of the run (row 0 = x0);
+ * u_cl: the actions applied; first_nonfinite: −1, or the global plant step index of the first non-finite plant state. The arrays
+ * of the run live in device buffers the handle owns and reuses; they are copied out after the one synchronise at the end. Refused
+ * (ILQR_ERR_INVALID) before any launch: a null descriptor, periods < 1, periods · steps > 2^20, everything ilqr_plant_step,
+ * ilqr_shift_horizon and ilqr_shift_duals refuse for these arguments (a handle with stage selectors among them), warm on a handle
+ * created unconstrained or without duals, either feedback without a policy. Works on a sharded handle: every device runs its
+ * shard's loop. */
+typedef struct {
+    int32_t periods;          /* P >= 1 re-solves */
+    int32_t steps;            /* k >= 1 control periods between re-solves */
+    int32_t plant_feedback;   /* the plant applies ū + K (x − x̄) instead of ū */
+    int32_t shift_feedback;   /* feedback argument of ilqr_shift_horizon */
+    int32_t shift_tail;       /* ILQR_SHIFT_TAIL_* */
+    int32_t warm;             /* 1: ilqr_shift_duals + ilqr_solve_warm; 0: ilqr_solve (cold) */
+    int32_t duals_tail, duals_penalty;   /* ILQR_DUALS_*; read when warm */
+    uint64_t seed; int64_t first_instance;
+    const double* sigma_x;    /* HOST, NULL or [nx] */
+} ilqr_mpc_desc;
+#define ILQR_MPC_LOG_W 9      /* objective, gradient_norm, max_violation, step_size, iterations, outer_iterations, status, potrf_info, rollouts — ilqr_stats order */
+int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d,
+                 const double* x0,          /* NULL (= x̄_0 of the handle), or [B][nx] */
+                 const double* w_plant,     /* NULL, or [B][P*k][nw_user] */
+                 double* x_cl,              /* NULL, or [B][P*k+1][nx] */
+                 double* u_cl,              /* NULL, or [B][P*k][nu] */
+                 double* log,               /* NULL, or [B][P][ILQR_MPC_LOG_W] */
+                 int32_t* first_nonfinite); /* NULL, or [B]: global plant step index, or -1 */
+
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):
  * the reference functions they run are listed per id. */
 enum {

@@ -44,6 +44,17 @@ class ModelSource(C.Structure):
                 ("flags", C.c_int32)]
 
 
+class ilqr_mpc_desc(C.Structure):
+    """The closed MPC loop of ilqr_mpc_run, under the header's own name. sigma_x is a host array the caller keeps alive over the call."""
+    _fields_ = [("periods", C.c_int32), ("steps", C.c_int32), ("plant_feedback", C.c_int32), ("shift_feedback", C.c_int32),
+                ("shift_tail", C.c_int32), ("warm", C.c_int32), ("duals_tail", C.c_int32), ("duals_penalty", C.c_int32),
+                ("seed", C.c_uint64), ("first_instance", C.c_int64), ("sigma_x", c_double_p)]
+
+
+MpcDesc = ilqr_mpc_desc
+MPC_LOG_W = 9
+MPC_LOG_COLUMNS = ("objective", "gradient_norm", "max_violation", "step_size", "iterations", "outer_iterations", "status", "potrf_info",
+                   "rollouts")
 MODEL_DENSE_TABLES = 1
 MAX_STAGE_KINDS = 16
 c_int32_p = C.POINTER(C.c_int32)
@@ -132,6 +143,11 @@ SYMBOLS = {
     "ilqr_shift_horizon_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "ilqr_shift_duals": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "ilqr_shift_duals_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "ilqr_plant_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                  c_double_p, c_double_p, C.POINTER(C.c_int32)]),
+    "ilqr_plant_step_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, c_double_p] + [C.c_void_p] * 5),
+    "ilqr_mpc_run": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                               C.POINTER(C.c_int32)]),
     "ilqr_solve": (C.c_int, [C.c_void_p]),
     "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),

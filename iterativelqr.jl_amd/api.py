@@ -32,6 +32,14 @@ def _p(a):
     return a.ctypes.data_as(_ffi.c_double_p)
 
 
+class MpcResult:
+    """What Solver.mpc_run_ returns: the closed-loop states x and actions u, the per-period log and first_nonfinite."""
+    __slots__ = ("x", "u", "log", "first_nonfinite")
+
+    def __init__(self, x, u, log, first_nonfinite):
+        self.x, self.u, self.log, self.first_nonfinite = x, u, log, first_nonfinite
+
+
 MODEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
                "-mllvm", "-amdgpu-mfma-vgpr-form",   # MFMA results straight into VGPRs (no AGPR copies)
                "-Wno-unused-parameter"]
@@ -315,6 +323,76 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_solve_warm(self._h))
         if sync:
             self.synchronize()
+
+    def _plant_arguments(self, steps, sigma_x, w_plant, rows):
+        steps = int(steps)
+        if not 1 <= steps <= self.T - 1:
+            raise ValueError("steps must lie in 1 .. T-1")
+        if sigma_x is not None:
+            sigma_x = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_x, dtype=np.float64), (self.nx,)))
+        if w_plant is not None:
+            w_plant = np.ascontiguousarray(w_plant, dtype=np.float64)
+            if self.num_user_parameter > 0 and w_plant.shape != (self.B, rows, self.num_user_parameter):
+                raise ValueError("w_plant must have shape [B, %d, num_parameter]" % rows)
+        return steps, sigma_x, w_plant
+
+    def plant_step_(self, x, steps=1, feedback=False, sigma_x=None, seed=0, first_instance=0, step0=0, w_plant=None):
+        """The plant of a closed MPC loop on the device (ilqr_plant_step): the plant states x [B, nx] move on by `steps` control
+        periods under the head of the handle's plan, u_i = ū_i, or with feedback=True ū_i + K_i (x − x̄_i); x ← f(x, u_i, w_i), then
+        x_j += sigma_x[j] · z with z = candidate_noise(seed, first_instance + b, 1 + j // 16, step0 + i, j % 16). w_plant [B, steps,
+        num_parameter]: the plant's own parameters (None: the handle's). Reads the handle; changes none of its state. Returns a dict
+        with x [B, steps + 1, nx] (row 0 the input states, the last row the new plant states), u [B, steps, nu] and first_nonfinite [B]
+        (−1, or the first step after which a state component is not finite)."""
+        steps, sigma_x, w_plant = self._plant_arguments(steps, sigma_x, w_plant, int(steps))
+        x = np.array(x, dtype=np.float64, order="C")
+        if x.shape != (self.B, self.nx):
+            raise ValueError("x must have shape [B, nx]")
+        out = dict(x=np.empty((self.B, steps + 1, self.nx)), u=np.empty((self.B, steps, self.nu)), first_nonfinite=np.empty(self.B, dtype=np.int32))
+        _ffi.check(_ffi.lib().ilqr_plant_step(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
+                                              _p(sigma_x) if sigma_x is not None else None, _p(w_plant) if w_plant is not None else None, _p(x),
+                                              _p(out["x"]), _p(out["u"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def plant_step_device_(self, d_x_ptr, steps=1, feedback=False, sigma_x=None, seed=0, first_instance=0, step0=0, d_w_plant_ptr=None,
+                           d_x_out_ptr=None, d_u_out_ptr=None, d_first_nonfinite_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not given / not wanted); d_x_ptr [B, nx] is updated in
+        place; sigma_x stays a host array; asynchronous on the handle's stream."""
+        steps, sigma_x, _ = self._plant_arguments(steps, sigma_x, None, int(steps))
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_plant_step_device(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
+                                                     _p(sigma_x) if sigma_x is not None else None, vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_x_out_ptr),
+                                                     vp(d_u_out_ptr), vp(d_first_nonfinite_ptr)))
+
+    def mpc_run_(self, periods, steps=1, x0=None, plant_feedback=False, shift_feedback=False, shift_tail="hold", warm=True, duals_tail="hold",
+                 duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None):
+        """The closed MPC loop, enqueued once and synchronised once (ilqr_mpc_run): for each of `periods` re-solves plant_step_(steps)
+        on a plant state that stays on the device, shift_horizon_(steps, x1 = the plant state), and shift_duals_ + solve_warm_ (warm)
+        or solve_. x0 [B, nx]: the first plant state (None: x̄_0 of the handle); w_plant [B, periods · steps, num_parameter]. Returns an
+        MpcResult with x [B, periods · steps + 1, nx], u [B, periods · steps, nu], log (a dict of [B, periods] arrays with the fields of
+        stats(), per re-solve) and first_nonfinite [B] (−1, or the global plant step after which a state was not finite)."""
+        periods = int(periods)
+        if periods < 1:
+            raise ValueError("periods must be >= 1")
+        steps, sigma_x, w_plant = self._plant_arguments(steps, sigma_x, w_plant, periods * int(steps))
+        for name, val, table in (("shift_tail", shift_tail, self._TAILS), ("duals_tail", duals_tail, self._TAILS), ("duals_penalty", duals_penalty, self._PENALTIES)):
+            if val not in table:
+                raise ValueError("%s must be one of %s" % (name, sorted(table)))
+        if x0 is not None:
+            x0 = np.ascontiguousarray(x0, dtype=np.float64)
+            if x0.shape != (self.B, self.nx):
+                raise ValueError("x0 must have shape [B, nx]")
+        _ffi.check(_ffi.lib().ilqr_set_options(self._h, C.byref(self.options)))
+        d = _ffi.MpcDesc(periods, steps, 1 if plant_feedback else 0, 1 if shift_feedback else 0, self._TAILS[shift_tail], 1 if warm else 0,
+                         self._TAILS[duals_tail], self._PENALTIES[duals_penalty], int(seed), int(first_instance),
+                         _p(sigma_x) if sigma_x is not None else None)
+        R = periods * steps
+        x, u = np.empty((self.B, R + 1, self.nx)), np.empty((self.B, R, self.nu))
+        log, nf = np.empty((self.B, periods, _ffi.MPC_LOG_W)), np.empty(self.B, dtype=np.int32)
+        _ffi.check(_ffi.lib().ilqr_mpc_run(self._h, C.byref(d), _p(x0) if x0 is not None else None, _p(w_plant) if w_plant is not None else None,
+                                           _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32))))
+        ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
+        return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)}, nf)
 
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""

@@ -94,11 +94,12 @@ long long ilqr::model_abi_word() { return ILQR_MODEL_ABI_VERSION * 1000 + (long 
 using ilqr::fail;
 using ilqr::find_model;
 
-// the stages (ilqr_handle::Stage) of ilqr_handle::pol, ::cand, ::shift and ::samp by name
+// the stages (ilqr_handle::Stage) of ilqr_handle::pol, ::cand, ::shift, ::samp and ::plant by name
 enum { POL_X1, POL_W, POL_COST, POL_VIOL, POL_NONFINITE, POL_X, POL_U, POL_STAGES };
 enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
 enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
+enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -159,6 +160,9 @@ struct ilqr_handle {
     // ilqr_shift_duals / ilqr_solve_warm: λ, ρ hold the duals of a solve (a constrained solve, the AL_BEGIN stage or a host write of
     // constraint_penalty since the last reset) — after a reset ρ is not a penalty ladder's and a warm solve would be refused
     bool has_duals = false;
+    // ilqr_plant_step: the device staging of its host form (the plant state in and out, w_plant, x_out, u_out, first_nonfinite);
+    // ilqr_mpc_run: the plant state, w_plant, the closed-loop trajectory, the log and first_nonfinite of the whole run
+    Stage plant[PLANT_STAGES];
 };
 
 namespace {
@@ -614,6 +618,7 @@ int ilqr_destroy(ilqr_handle* h) {
     for (auto& st : h->cand) if (st.p) hipFree(st.p);
     for (auto& st : h->shift) if (st.p) hipFree(st.p);
     for (auto& st : h->samp) if (st.p) hipFree(st.p);
+    for (auto& st : h->plant) if (st.p) hipFree(st.p);
     if (h->trace) hipFree(h->trace);
     if (h->qv) hipFree(h->qv);
     if (h->stream) hipStreamDestroy(h->stream);
@@ -1323,6 +1328,140 @@ int ilqr_shift_duals(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalt
     ILQR_TRY(ilqr_shift_duals_device(h, steps, tail, penalty));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
+}
+
+// ---- the plant of a closed MPC loop (ilqr_device_plant.hpp): the head of the plan applied to the dynamics from a plant state in HBM
+// everything that can be refused without touching the GPU; what needs no handle comes first
+static int plant_check(const ilqr_handle* h, int32_t steps, int32_t feedback, int64_t first_instance, int64_t step0, int64_t total_steps,
+                       const double* sigma_x, const double* w_plant, const char* who) {
+    const std::string me(who);
+    if (steps < 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
+    if (step0 < 0 || step0 + total_steps > ilqr::PLANT_MAX_STEPS) return fail(ILQR_ERR_INVALID, me + ": step0 >= 0 and no plant step index beyond 2^20 (the noise key's bit fields)");
+    if (first_instance < 0 || first_instance >= ilqr::PLANT_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance must lie in 0 .. 2^23 - 1");
+    if (sigma_x && (!(sigma_x[0] >= 0.0) || !std::isfinite(sigma_x[0]))) return fail(ILQR_ERR_INVALID, me + ": sigma_x must be finite and >= 0");
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (steps > h->L.T - 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
+    if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
+    for (int j = 0; sigma_x && j < h->L.nx; ++j)
+        if (!(sigma_x[j] >= 0.0) || !std::isfinite(sigma_x[j])) return fail(ILQR_ERR_INVALID, me + ": sigma_x must be finite and >= 0");
+    if (first_instance + (int64_t)h->B > ilqr::PLANT_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance + batch must not exceed 2^23");
+    if (w_plant && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_plant given, but this model has no parameters (num_parameter == 0)");
+    if (feedback && !every_shard_holds(h, &ilqr_handle::has_policy))
+        return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
+    return ILQR_OK;
+}
+
+// what a plant launch takes of the handle and of the call; the arrays are the caller's to fill in
+static ilqr::PlantArgs plant_args(const ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                                  const double* sigma_x) {
+    ilqr::PlantArgs a = {};
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.feedback = feedback ? 1 : 0; a.n_sel = h->n_sel; a.step0 = step0;
+    a.noise = sigma_x != nullptr; a.nf_global = 0; a.seed = seed; a.b0 = first_instance;
+    for (int j = 0; sigma_x && j < h->L.nx; ++j) a.sigma[j] = sigma_x[j];      // by value: the caller's array may go away at once
+    return a;
+}
+
+// every pointer null or a device pointer on h's device; the arrays of ONE call: `steps` rows per instance (x_out: one more)
+static int plant_launch(ilqr_handle* h, ilqr::PlantArgs a, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
+    if (!h->vt->launch_plant) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
+    a.w = w_plant; a.x = x; a.x_out = x_out; a.u_out = u_out; a.nonfinite = first_nonfinite;
+    a.w_ld = a.steps; a.x_ld = a.steps + 1; a.u_ld = a.steps;
+    if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_plant_step_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                           const double* sigma_x, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
+    if (!x) return fail(ILQR_ERR_INVALID, "ilqr_plant_step_device: null x");
+    ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, w_plant, "ilqr_plant_step_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_plant_step");
+    HIP_TRY(hipSetDevice(h->device));
+    return plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x), w_plant, x, x_out, u_out, first_nonfinite);
+}
+
+int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                    const double* sigma_x, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
+    if (!x) return fail(ILQR_ERR_INVALID, "ilqr_plant_step: null x");
+    ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, w_plant, "ilqr_plant_step"));
+    const size_t k = (size_t)steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_plant_step(s, steps, feedback, seed, first_instance + (int64_t)lo, step0, sigma_x, at(w_plant, lo * k * nwu), x + lo * n,
+                               at(x_out, lo * (k + 1) * n), at(u_out, lo * k * m), at(first_nonfinite, lo)); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    const Staged s_x = {&h->plant[PLANT_X], x, x, B * n * 8};                // the plant state goes in and comes back
+    const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * k * nwu * 8);
+    const Staged s_x_out = staged_out(h->plant[PLANT_X_OUT], x_out, B * (k + 1) * n * 8);
+    const Staged s_u_out = staged_out(h->plant[PLANT_U_OUT], u_out, B * k * m * 8);
+    const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
+    const auto arrays = {s_x, s_w, s_x_out, s_u_out, s_nonfinite};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x), s_w.dev<const double>(), s_x.dev<double>(),
+                          s_x_out.dev<double>(), s_u_out.dev<double>(), s_nonfinite.dev<int32_t>()));
+    return stage_out(h, arrays);
+}
+
+// ---- the closed MPC loop, enqueued once: per period plant step, horizon shift, dual shift, solve, log row
+static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
+// everything its constituents refuse for these arguments, before any launch
+static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const double* w_plant) {
+    const std::string me("ilqr_mpc_run");
+    if (!d) return fail(ILQR_ERR_INVALID, me + ": null descriptor");
+    if (d->periods < 1) return fail(ILQR_ERR_INVALID, me + ": periods must be >= 1");
+    ILQR_TRY(plant_check(h, d->steps, d->plant_feedback, d->first_instance, 0, (int64_t)d->periods * (int64_t)(d->steps > 0 ? d->steps : 0),
+                         d->sigma_x, w_plant, "ilqr_mpc_run"));
+    ILQR_TRY(shift_check(h, d->steps, d->shift_tail, d->shift_feedback, nullptr, "ilqr_mpc_run"));
+    if (d->warm) {
+        if (!h->constrained) return fail(ILQR_ERR_INVALID, me + ": warm on a handle created unconstrained: it has no duals to keep");
+        ILQR_TRY(duals_check(h, d->steps, d->duals_tail, d->duals_penalty, "ilqr_mpc_run"));
+    }
+    return ILQR_OK;
+}
+
+int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, double* x_cl, double* u_cl, double* log,
+                 int32_t* first_nonfinite) {
+    ILQR_TRY(mpc_check(h, d, w_plant));
+    const size_t P = (size_t)d->periods, k = (size_t)d->steps, R = P * k, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        ilqr_mpc_desc sd = *d;
+        sd.first_instance += (int64_t)lo;
+        return ilqr_mpc_run(s, &sd, at(x0, lo * n), at(w_plant, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
+                            at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo)); }, true);
+    if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    const Staged s_x = staged_in(h->plant[PLANT_X], x0, B * n * 8);
+    const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * R * nwu * 8);
+    const Staged s_x_cl = staged_out(h->plant[PLANT_X_OUT], x_cl, B * (R + 1) * n * 8);
+    const Staged s_u_cl = staged_out(h->plant[PLANT_U_OUT], u_cl, B * R * m * 8);
+    const Staged s_log = staged_out(h->plant[PLANT_LOG], log, B * P * ILQR_MPC_LOG_W * 8);
+    const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
+    const auto arrays = {s_x, s_w, s_x_cl, s_u_cl, s_log, s_nonfinite};
+    // Every buffer of the run exists before its first launch — the plant state also without an x0, and what the shift would allocate
+    // in its first call — so that nothing between the first plant launch and the synchronise at the end waits for the device.
+    ILQR_TRY(grow(h, h->plant[PLANT_X], B * n * 8));
+    ILQR_TRY(resident_inputs(h));
+    if (h->L.nw > 0) ILQR_TRY(grow(h, h->shift[SHIFT_W_STAGE], B * (size_t)h->L.T * (size_t)h->L.nw * 8));
+    ILQR_TRY(stage_in(h, arrays));
+    double* xp = (double*)h->plant[PLANT_X].p;
+    if (!x0) HIP_TRY(hipMemcpy2DAsync(xp, n * 8, h->ws + h->L.xb, (size_t)h->L.stride * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
+    if (s_nonfinite.bytes) HIP_TRY(hipMemsetAsync(s_nonfinite.st->p, 0xff, B * 4, h->stream));       // -1: the plant kernel keeps the first mark
+    for (int32_t p = 0; p < d->periods; ++p) {
+        ilqr::PlantArgs a = plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, d->sigma_x);
+        a.w = s_w.dev<const double>(); a.x = xp; a.x_out = s_x_cl.dev<double>(); a.u_out = s_u_cl.dev<double>(); a.nonfinite = s_nonfinite.dev<int32_t>();
+        a.nf_global = 1;
+        a.w_ld = (long long)R; a.x_ld = (long long)R + 1; a.u_ld = (long long)R;                     // rows p·k .. of the run's arrays
+        a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
+        if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
+        ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, xp, nullptr));
+        if (d->warm) ILQR_TRY(ilqr_shift_duals_device(h, d->steps, d->duals_tail, d->duals_penalty));
+        ILQR_TRY(d->warm ? ilqr_solve_warm(h) : ilqr_solve(h));
+        if (s_log.bytes) {
+            a.log = s_log.dev<double>(); a.log_ld = d->periods; a.log_row = p;
+            if (h->vt->launch_mpc_log(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "log launch failed");
+        }
+    }
+    return stage_out(h, arrays);               // the one synchronise of the run
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

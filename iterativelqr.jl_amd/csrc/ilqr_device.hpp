@@ -2329,10 +2329,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_sample.hpp"
 #include "ilqr_device_shift.hpp"
 #include "ilqr_device_duals.hpp"
+#include "ilqr_device_plant.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 16   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 17   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2363,6 +2364,10 @@ extern "C" struct ilqr_model_vtable {
     int (*launch_sample_candidates)(const ilqr::SampleArgs* a, void* stream);
     // receding-horizon shift of the duals and penalties, in place in the workspace (ilqr_device_duals.hpp)
     int (*launch_shift_duals)(const ilqr::DualsArgs* a, void* stream);
+    // the plant of a closed MPC loop: the head of the plan applied to the dynamics from a plant state in HBM; reads the workspace
+    // only (ilqr_device_plant.hpp). launch_mpc_log: the nine scalars of ilqr_stats of every instance into one row of the loop's log
+    int (*launch_plant)(const ilqr::PlantArgs* a, void* stream);
+    int (*launch_mpc_log)(const ilqr::PlantArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2423,7 +2428,8 @@ struct ModelModule {
                                              &launch, kernels, &launch_init,
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
-                                             &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>, &launch_shift_duals<M>};
+                                             &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>, &launch_shift_duals<M>,
+                                             &launch_plant<M>, &launch_mpc_log<M>};
         return &vt;
     }
 };

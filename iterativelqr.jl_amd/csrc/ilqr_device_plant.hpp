@@ -1,0 +1,217 @@
+// The plant of a closed MPC loop on the device (ilqr_plant_step, ilqr_mpc_run, include/ilqr_hip.h): the head of the handle's plan
+// applied to the model's own dynamics from a plant state that lives in HBM. With k = steps, g = step0 + i the global plant step and
+// x̄, ū, K, θ as the workspace holds them, for i = 0 .. k−1
+//
+//   u_i = ū_i                       (feedback == 0)
+//   u_i = ū_i + K_i (x − x̄_i)       (feedback != 0; src/rollout.jl:24-28 with α = 0, formed as (ū + K x) − K x̄: plant_feedback_row,
+//                                    the arithmetic of shift_feedback_kernel / shift_feedback_large_kernel at s = i)
+//   w_i = the user's columns of w_plant[b][i] if given, else of θ_i; the selector columns of a lowered problem are θ_i's
+//   x ← f(x, u_i, w_i),  then  x_j ← x_j + sigma_x[j] · z(seed, b0 + b, 1 + j / 16, g, j % 16)   for every j with sigma_x[j] != 0
+//
+// (product and sum rounded separately). z is sample_z (ilqr_device_sample.hpp), unchanged: the key's candidate field carries the
+// state component's high bits offset by one, its step field the global plant step, so ilqr_candidate_noise(seed, b0, B,
+// 1 + ceil(nx / 16), step0 + k, 16, z) is the host twin — its row 0 is zero by contract, and the offset keeps every drawn
+// component out of it. The fields stay disjoint for nx <= 64 (candidate <= 4), g < 2^20, b0 + b < 2^23: the entry points refuse
+// anything beyond.
+//
+// The kernels READ the workspace and write only the caller's plant arrays: x (in place, every lane or wave its own instance's row:
+// read once at the start, written once at the end), x_out, u_out, first_nonfinite. No atomics, no cross-instance traffic.
+//
+// plant_step_kernel (nx, nu <= 4): ONE INSTANCE PER LANE as shift_feedback_kernel and init_rollout_kernel, the state in registers,
+// generated M::dyn: an instance's bits depend neither on B nor on its neighbours.
+// plant_step_large_kernel: ONE WAVE PER INSTANCE as shift_feedback_large_kernel / policy_rollout_large_kernel (DynAff / dyn_row, row
+// i of K_i on lane i, x, u and w_i through LDS). Lane j < nx owns state row j and draws that row's noise: rows beyond lane 15 have
+// their own key (candidate field 1 + j / 16).
+//
+// mpc_log_kernel: one thread per (instance, column) copies the nine scalars of ilqr_stats out of the scalar block into row p of
+// the log. Plain vector stores.
+#pragma once
+
+#include <stdint.h>
+
+namespace ilqr {
+
+enum { PLANT_MAX_NX = 64, PLANT_MAX_STEPS = 1 << 20, PLANT_MAX_INSTANCES = 1 << 23, MPC_LOG_W = 9, MPC_LOG_THREADS = 256 };
+
+struct PlantArgs {
+    const double* ws;        // the handle's workspace (read-only here)
+    Layout L;
+    int B;
+    int steps;               // k, 1 .. T-1
+    int feedback;
+    int n_sel;               // trailing parameter columns that stay the handle's (stage selectors) when w is given
+    int step0;               // global index of plant step 0 of this call
+    int noise;               // sigma holds a vector (some entry may still be 0)
+    int nf_global;           // 0: first_nonfinite is written, -1 or the local step i; 1: it is kept when >= 0, else -1 or step0 + i
+    uint64_t seed;
+    long long b0;            // global index of the handle's instance 0
+    double sigma[PLANT_MAX_NX];   // sigma_x by value: the first nx entries
+    const double* w;         // null, or rows of nw - n_sel doubles: row (b · w_ld + w_row0 + i)
+    double* x;               // [B][nx] in / out
+    double* x_out;           // null, or rows of nx doubles: row (b · x_ld + x_row0 + i), i = 0 .. k (row 0 = the input state)
+    double* u_out;           // null, or rows of nu doubles: row (b · u_ld + u_row0 + i), i = 0 .. k-1
+    int* nonfinite;          // null, or [B]
+    long long w_ld, w_row0, x_ld, x_row0, u_ld, u_row0;
+    // mpc_log_kernel
+    double* log;             // [B][log_ld][MPC_LOG_W]
+    int log_ld, log_row;
+};
+
+// row i of ū_s + K_s (x − x̄_s) with x read through xv(j): kx and kb are the two FMA chains over j = 0 .. n−1, then (ū + kx) − kb
+template <class M, class XV>
+__device__ __forceinline__ double plant_feedback_row(const double* g, const Layout& L, int s, int i, XV xv) {
+    constexpr int n = M::NX, m = M::NU, KN = m * n;
+    const double* Ks = g + L.K + s * KN;
+    double kx = 0.0, kb = 0.0;
+#pragma unroll
+    for (int j = 0; j < n; ++j) { kx = fma(Ks[j * m + i], xv(j), kx); kb = fma(Ks[j * m + i], g[L.xb + s * n + j], kb); }
+    return (g[L.ub + s * m + i] + kx) - kb;                                                        // (:24-28), α = 0
+}
+
+__device__ __forceinline__ double plant_noise(const PlantArgs& a, double x, double sigma, int b, int i, int j) {
+    return __dadd_rn(x, __dmul_rn(sigma, sample_z(a.seed, a.b0 + b, 1 + j / 16, a.step0 + i, j % 16)));
+}
+
+// what first_nonfinite gets: the first step with a non-finite state, local or global, or what an earlier call of the loop left
+__device__ __forceinline__ int plant_nf_in(const PlantArgs& a, int b) { return (a.nonfinite && a.nf_global) ? a.nonfinite[b] : -1; }
+__device__ __forceinline__ int plant_nf_mark(const PlantArgs& a, int nf, bool fin, int i) {
+    return (nf < 0 && !fin) ? (a.nf_global ? a.step0 + i : i) : nf;
+}
+
+template <class M>
+__global__ __launch_bounds__(64) void plant_step_kernel(PlantArgs a) {
+    constexpr int n = M::NX, m = M::NU, NW = M::NW;
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= a.B) return;
+    const Layout& L = a.L;
+    const double* g = a.ws + (size_t)b * (size_t)L.stride;
+    const int k = a.steps, nwu = NW - a.n_sel;
+    const double* wp = a.w ? a.w + ((size_t)b * (size_t)a.w_ld + (size_t)a.w_row0) * (size_t)(nwu > 0 ? nwu : 0) : nullptr;
+    double* xo = a.x_out ? a.x_out + ((size_t)b * (size_t)a.x_ld + (size_t)a.x_row0) * n : nullptr;
+    double* uo = a.u_out ? a.u_out + ((size_t)b * (size_t)a.u_ld + (size_t)a.u_row0) * m : nullptr;
+    double xt[n];
+#pragma unroll
+    for (int i = 0; i < n; ++i) xt[i] = a.x[(size_t)b * n + i];
+    if (xo) {
+#pragma unroll
+        for (int i = 0; i < n; ++i) xo[i] = xt[i];
+    }
+    int nf = plant_nf_in(a, b);
+    for (int i = 0; i < k; ++i) {
+        double ut[m], y[n];
+#pragma unroll
+        for (int r = 0; r < m; ++r)
+            ut[r] = a.feedback ? plant_feedback_row<M>(g, L, i, r, [&](int j) { return xt[j]; }) : g[L.ub + i * m + r];
+        if (uo) {
+#pragma unroll
+            for (int r = 0; r < m; ++r) uo[(size_t)i * m + r] = ut[r];
+        }
+        double w[cdim<NW>::v];
+        load_w<NW>(g + L.w, i, w);
+        if constexpr (NW > 0) {
+            if (wp) {
+#pragma unroll
+                for (int j = 0; j < NW; ++j)
+                    if (j < nwu) w[j] = wp[(size_t)i * nwu + j];
+            }
+        }
+        M::dyn(xt, ut, w, y);                                                                  // (:29)
+        bool fin = true;
+#pragma unroll
+        for (int j = 0; j < n; ++j) {
+            if (a.noise && a.sigma[j] != 0.0) y[j] = plant_noise(a, y[j], a.sigma[j], b, i, j);      // (the same branch on every lane)
+            xt[j] = y[j];
+            fin = fin && (fabs(y[j]) < __builtin_huge_val());                                  // false for ±Inf and NaN
+        }
+        nf = plant_nf_mark(a, nf, fin, i);
+        if (xo) {
+#pragma unroll
+            for (int j = 0; j < n; ++j) xo[(size_t)(i + 1) * n + j] = xt[j];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < n; ++i) a.x[(size_t)b * n + i] = xt[i];
+    if (a.nonfinite) a.nonfinite[b] = nf;
+}
+
+template <class M>
+__global__ __launch_bounds__(64) void plant_step_large_kernel(PlantArgs a) {
+    constexpr int n = M::NX, m = M::NU, NW = M::NW;
+    static_assert(n <= PLANT_MAX_NX, "sigma_x travels by value");
+    __shared__ double sx[n], su[m], sw[cdim<NW>::v];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.B) return;
+    const Layout& L = a.L;
+    const double* g = a.ws + (size_t)b * (size_t)L.stride;
+    const int k = a.steps, nwu = NW - a.n_sel;
+    const double* wp = a.w ? a.w + ((size_t)b * (size_t)a.w_ld + (size_t)a.w_row0) * (size_t)(nwu > 0 ? nwu : 0) : nullptr;
+    double* xo = a.x_out ? a.x_out + ((size_t)b * (size_t)a.x_ld + (size_t)a.x_row0) * n : nullptr;
+    double* uo = a.u_out ? a.u_out + ((size_t)b * (size_t)a.u_ld + (size_t)a.u_row0) * m : nullptr;
+    DynAff<M> aff;
+    aff.init(lane);
+    const int xrow = DynAff<M>::SPLIT ? (lane & 31) : lane;
+    double xl = xrow < n ? a.x[(size_t)b * n + xrow] : 0.0;
+    double sg = 0.0;                                                          // sigma_x of the row this lane owns (lane < nx)
+    if (a.noise) {
+#pragma unroll
+        for (int j = 0; j < n; ++j) sg = (lane == j) ? a.sigma[j] : sg;
+    }
+    int nf = plant_nf_in(a, b);
+    if (lane == 0) sw[0] = 0.0;
+    for (int i = 0; i < k; ++i) {
+        if (lane < n) { sx[lane] = xl; if (xo) xo[(size_t)i * n + lane] = xl; }
+        for (int j = lane; j < NW; j += 64) sw[j] = (wp && j < nwu) ? wp[(size_t)i * nwu + j] : g[L.w + i * NW + j];
+        wave_lds_fence();
+        policy_wave_sync();
+        if (lane < m) {                                                       // row `lane` of K_i
+            const double v = a.feedback ? plant_feedback_row<M>(g, L, i, lane, [&](int j) { return sx[j]; }) : g[L.ub + i * m + lane];
+            su[lane] = v;
+            if (uo) uo[(size_t)i * m + lane] = v;
+        }
+        wave_lds_fence();
+        policy_wave_sync();
+        double ua[m];
+#pragma unroll
+        for (int j = 0; j < m; ++j) ua[j] = su[j];
+        xl = dyn_row<M>(aff, sx, ua, xl, lane, sw, 0);                        // (:29)
+        if (sg != 0.0) xl = plant_noise(a, xl, sg, b, i, lane);               // (lanes that own no row have sg == 0)
+        const bool bad = lane < n && !(fabs(xl) < __builtin_huge_val());
+        nf = plant_nf_mark(a, nf, __ballot(bad) == 0ull, i);
+        wave_lds_fence();
+        policy_wave_sync();                                                   // sx, su, sw are rewritten by the next step
+    }
+    if (lane < n) { a.x[(size_t)b * n + lane] = xl; if (xo) xo[(size_t)k * n + lane] = xl; }
+    if (lane == 0 && a.nonfinite) a.nonfinite[b] = nf;
+}
+
+// Templated on the model only so that every module carries its own copy (the kernel reads nothing of M: the Layout has it all).
+template <class M>
+__global__ __launch_bounds__(MPC_LOG_THREADS) void mpc_log_kernel(PlantArgs a) {
+    const int e = blockIdx.x * MPC_LOG_THREADS + threadIdx.x;
+    if (e >= a.B * MPC_LOG_W) return;
+    const int b = e / MPC_LOG_W, c = e % MPC_LOG_W;
+    // ilqr_stats order
+    const int slot = c == 0 ? S_OBJECTIVE : c == 1 ? S_GRADIENT_NORM : c == 2 ? S_MAX_VIOLATION : c == 3 ? S_STEP_SIZE : c == 4 ? S_ITERATIONS
+                   : c == 5 ? S_OUTER_ITERATIONS : c == 6 ? S_STATUS : c == 7 ? S_POTRF_INFO : S_ROLLOUTS;
+    a.log[((size_t)b * (size_t)a.log_ld + (size_t)a.log_row) * MPC_LOG_W + c] = a.ws[(size_t)b * (size_t)a.L.stride + a.L.scal + slot];
+}
+
+template <class M>
+int launch_plant(const PlantArgs* a, void* stream) {
+    if (a->B < 1 || a->steps < 1 || a->steps > a->L.T - 1 || !a->x || M::NX > PLANT_MAX_NX) return -1;
+    if constexpr (is_large<M>::value)
+        hipLaunchKernelGGL(plant_step_large_kernel<M>, dim3((unsigned)a->B), dim3(64), 0, (hipStream_t)stream, *a);
+    else
+        hipLaunchKernelGGL(plant_step_kernel<M>, dim3((unsigned)((a->B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, *a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template <class M>
+int launch_mpc_log(const PlantArgs* a, void* stream) {
+    if (a->B < 1 || !a->log || a->log_row < 0 || a->log_row >= a->log_ld) return -1;
+    const size_t grid = ((size_t)a->B * MPC_LOG_W + MPC_LOG_THREADS - 1) / MPC_LOG_THREADS;
+    hipLaunchKernelGGL(mpc_log_kernel<M>, dim3((unsigned)grid), dim3(MPC_LOG_THREADS), 0, (hipStream_t)stream, *a);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace ilqr

@@ -13,8 +13,10 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
+
+import Libdl
 
 const LIB = Ref{String}(joinpath(@__DIR__, "..", "lib", "libilqr_hip.so"))
 
@@ -213,6 +215,74 @@ function solve_warm!(s::Solver)
     check(ccall((:ilqr_solve_warm, LIB[]), Cint, (Ptr{Cvoid},), s.handle))
     check(ccall((:ilqr_synchronize, LIB[]), Cint, (Ptr{Cvoid},), s.handle))
     return nothing
+end
+
+# The plant of a closed MPC loop on the device (ilqr_plant_step): the plant states x :: (nx, B) move on by `steps` control periods
+# under the head of the handle's plan, u_i = ū_i or (feedback) ū_i + K_i (x − x̄_i), x ← f(x, u_i, w_i) + sigma_x .* z with z the noise
+# of candidate_noise at candidate 1 + j ÷ 16, step step0 + i, component j % 16. w_plant :: (nw, steps, B): the plant's own parameters.
+# Reads the handle. Returns (x_out :: (nx, steps + 1, B), u_out :: (nu, steps, B), first_nonfinite :: B); x is updated in place.
+function plant_step!(s::Solver, x::Matrix{Float64}; steps::Integer = 1, feedback::Bool = false, seed::Integer = 0,
+                     first_instance::Integer = 0, step0::Integer = 0, sigma_x::Union{Nothing,Vector{Float64}} = nothing,
+                     w_plant::Union{Nothing,Array{Float64,3}} = nothing)
+    @assert 1 <= steps <= s.T - 1 && size(x) == (s.nx, s.B)
+    @assert sigma_x === nothing || length(sigma_x) == s.nx
+    @assert w_plant === nothing || (size(w_plant, 2) == steps && size(w_plant, 3) == s.B)
+    nul = Ptr{Float64}(C_NULL)
+    x_out = Array{Float64,3}(undef, s.nx, steps + 1, s.B)
+    u_out = Array{Float64,3}(undef, s.nu, steps, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_plant_step, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                s.handle, Int32(steps), Int32(feedback ? 1 : 0), UInt64(seed), Int64(first_instance), Int32(step0),
+                sigma_x === nothing ? nul : sigma_x, w_plant === nothing ? nul : w_plant, x, x_out, u_out, nf))
+    return x_out, u_out, nf
+end
+
+# ilqr_mpc_desc, field for field
+struct MpcDesc
+    periods::Int32
+    steps::Int32
+    plant_feedback::Int32
+    shift_feedback::Int32
+    shift_tail::Int32
+    warm::Int32
+    duals_tail::Int32
+    duals_penalty::Int32
+    seed::UInt64
+    first_instance::Int64
+    sigma_x::Ptr{Float64}
+end
+
+# The closed MPC loop, enqueued once (ilqr_mpc_run): per period plant_step!, shift_horizon! from the plant state, (warm) shift_duals!
+# and solve_warm!, else solve!, and a log row with the fields of Stats as Float64. x0 :: (nx, B) (nothing: x̄ at step 1 of the handle).
+# Returns (x :: (nx, periods·steps + 1, B), u :: (nu, periods·steps, B), log :: (9, periods, B), first_nonfinite :: B).
+# (The symbol is looked up by hand: the descriptor travels as Ref{MpcDesc}.)
+function mpc_run!(s::Solver; periods::Integer, steps::Integer = 1, plant_feedback::Bool = false, shift_feedback::Bool = false,
+                  shift_tail::Symbol = :hold, warm::Bool = true, duals_tail::Symbol = :hold, duals_penalty::Symbol = :keep,
+                  seed::Integer = 0, first_instance::Integer = 0, sigma_x::Union{Nothing,Vector{Float64}} = nothing,
+                  x0::Union{Nothing,Matrix{Float64}} = nothing, w_plant::Union{Nothing,Array{Float64,3}} = nothing)
+    @assert periods >= 1 && 1 <= steps <= s.T - 1
+    @assert sigma_x === nothing || length(sigma_x) == s.nx
+    @assert x0 === nothing || size(x0) == (s.nx, s.B)
+    R = periods * steps
+    @assert w_plant === nothing || (size(w_plant, 2) == R && size(w_plant, 3) == s.B)
+    nul = Ptr{Float64}(C_NULL)
+    x = Array{Float64,3}(undef, s.nx, R + 1, s.B)
+    u = Array{Float64,3}(undef, s.nu, R, s.B)
+    log = Array{Float64,3}(undef, 9, periods, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    sig = sigma_x === nothing ? Float64[] : sigma_x
+    GC.@preserve sig begin
+        d = MpcDesc(Int32(periods), Int32(steps), Int32(plant_feedback ? 1 : 0), Int32(shift_feedback ? 1 : 0),
+                    Int32(shift_tail === :hold ? 0 : 1), Int32(warm ? 1 : 0), Int32(duals_tail === :hold ? 0 : 1),
+                    Int32(duals_penalty === :keep ? 0 : 1), UInt64(seed), Int64(first_instance),
+                    sigma_x === nothing ? nul : pointer(sig))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_mpc_run)
+        check(ccall(fn, Cint, (Ptr{Cvoid}, Ref{MpcDesc}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                    s.handle, d, x0 === nothing ? nul : x0, w_plant === nothing ? nul : w_plant, x, u, log, nf))
+    end
+    return x, u, log, nf
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
