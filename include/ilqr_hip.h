@@ -318,6 +318,50 @@ int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d,
                  double* log,               /* NULL, or [B][P][ILQR_MPC_LOG_W] */
                  int32_t* first_nonfinite); /* NULL, or [B]: global plant step index, or -1 */
 
+/* The score of plant steps, on the device: the realised stage cost and constraint violation of the states a plant visited and the
+ * actions it applied — what a closed loop is judged by, as opposed to the predicted objective and violation of ilqr_stats. For
+ * i = 0 .. k−1, k = `steps`, with x_i = x[b][i] (the state the action was applied from) and u_i = u[b][i]:
+ *     w_i = the user's columns of w_plant[b][i] if given, else of θ_i as the handle holds them when the call is made; the selector
+ *           columns of a lowered problem are always θ_i's   (the rule of ilqr_plant_step)
+ *     cost[b][i]      = the stage cost at (x_i, u_i, w_i)     (src/costs.jl:48-55: one stage term; no terminal term)
+ *     violation[b][i] = max over the stage constraint rows of max(0, c) (inequality rows) or |c| (equality rows) at (x_i, u_i, w_i),
+ *                       NaN-propagating (src/data/constraints.jl:23-39); 0 on a handle created unconstrained or when nc_stage == 0
+ * Nothing is summed: every element is a pure function of its own three rows, so its bits depend neither on the batch nor on
+ * `steps` nor on its neighbours, and a non-finite row reaches no other element. To be called while the handle still holds the plan
+ * the steps were taken under (ilqr_shift_horizon overwrites θ_0 .. θ_{k−1}). The call READS the handle, as ilqr_plant_step does.
+ * Refused (ILQR_ERR_INVALID) without touching the GPU: steps < 1 or > T−1, a null x, u or cost, a null handle, w_plant on a model
+ * without user parameters. Host form: stages through device buffers the handle owns and reuses, works on a sharded handle,
+ * synchronous. Device form: every pointer a device pointer on the handle's device, asynchronous on the handle's stream; refused on
+ * a sharded handle. */
+int ilqr_plant_score(ilqr_handle* h, int32_t steps,
+                     const double* w_plant,     /* NULL, or [B][steps][nw_user] */
+                     const double* x,           /* [B][steps+1][nx]: ilqr_plant_step's x_out (row `steps` is not read) */
+                     const double* u,           /* [B][steps][nu]:   ilqr_plant_step's u_out */
+                     double* cost,              /* [B][steps] */
+                     double* violation);        /* NULL, or [B][steps] */
+int ilqr_plant_score_device(ilqr_handle* h, int32_t steps, const double* d_w_plant, const double* d_x, const double* d_u, double* d_cost,
+                            double* d_violation);
+
+/* ilqr_mpc_run following a previewed parameter stream, and scored. Per period p the loop of ilqr_mpc_run gains
+ *   1b. cl_cost given: ilqr_plant_score_device(k, w_plant rows p·k .., the plant states and actions of step 1) into rows p·k .. p·k+k−1
+ *       of cl_cost / cl_violation — before the shift, which overwrites the θ rows the plant ran under
+ *   2.  w_preview given: ilqr_shift_horizon_device(..., w_tail = rows p·k .. p·k+k−1 of w_preview[b]) — the k parameter rows that
+ *       enter the horizon are the caller's (a reference trajectory, a moving obstacle, a scheduled set-point) instead of copies of
+ *       the old last row. After P periods θ_t is the original θ_{t+P·k} where t + P·k <= T−1, else w_preview[b][t + P·k − T].
+ * With w_preview, cl_cost and cl_violation NULL the call is ilqr_mpc_run, bit for bit. Still one enqueue and one synchronise; every
+ * buffer of the run is allocated before its first launch. Refused (ILQR_ERR_INVALID) before any launch: everything ilqr_mpc_run
+ * refuses, w_preview on a model without user parameters, cl_violation without cl_cost. Works on a sharded handle. */
+int ilqr_mpc_run_preview(ilqr_handle* h, const ilqr_mpc_desc* d,
+                         const double* x0,          /* NULL (= x̄_0 of the handle), or [B][nx] */
+                         const double* w_plant,     /* NULL, or [B][P*k][nw_user] */
+                         const double* w_preview,   /* NULL, or [B][P*k][nw_user] */
+                         double* x_cl,              /* NULL, or [B][P*k+1][nx] */
+                         double* u_cl,              /* NULL, or [B][P*k][nu] */
+                         double* log,               /* NULL, or [B][P][ILQR_MPC_LOG_W] */
+                         int32_t* first_nonfinite,  /* NULL, or [B]: global plant step index, or -1 */
+                         double* cl_cost,           /* NULL, or [B][P*k]: realised stage cost of every plant step */
+                         double* cl_violation);     /* NULL, or [B][P*k]: realised stage violation; needs cl_cost */
+
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):
  * the reference functions they run are listed per id. */
 enum {

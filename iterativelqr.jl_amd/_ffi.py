@@ -148,7 +148,11 @@ SYMBOLS = {
     "ilqr_plant_step_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, c_double_p] + [C.c_void_p] * 5),
     "ilqr_mpc_run": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                C.POINTER(C.c_int32)]),
-    "ilqr_solve": (C.c_int, [C.c_void_p]),
+    "ilqr_plant_score": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "ilqr_plant_score_device": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    "ilqr_mpc_run_preview": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                       C.POINTER(C.c_int32), c_double_p, c_double_p]),
+    "ilqr_solve":(C.c_int, [C.c_void_p]),
     "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),
     "ilqr_solve_shared_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_double_p, C.c_int32, C.POINTER(C.c_int32)]),

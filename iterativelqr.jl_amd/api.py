@@ -33,11 +33,13 @@ def _p(a):
 
 
 class MpcResult:
-    """What Solver.mpc_run_ returns: the closed-loop states x and actions u, the per-period log and first_nonfinite."""
-    __slots__ = ("x", "u", "log", "first_nonfinite")
+    """What Solver.mpc_run_ returns: the closed-loop states x and actions u, the per-period log and first_nonfinite; with score=True
+    the realised stage cost and violation of every plant step, cl_cost and cl_violation [B, periods · steps] (None otherwise)."""
+    __slots__ = ("x", "u", "log", "first_nonfinite", "cl_cost", "cl_violation")
 
-    def __init__(self, x, u, log, first_nonfinite):
+    def __init__(self, x, u, log, first_nonfinite, cl_cost=None, cl_violation=None):
         self.x, self.u, self.log, self.first_nonfinite = x, u, log, first_nonfinite
+        self.cl_cost, self.cl_violation = cl_cost, cl_violation
 
 
 MODEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -364,17 +366,49 @@ class Solver:
                                                      _p(sigma_x) if sigma_x is not None else None, vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_x_out_ptr),
                                                      vp(d_u_out_ptr), vp(d_first_nonfinite_ptr)))
 
+    def plant_score_(self, x, u, w_plant=None):
+        """The score of plant steps on the device (ilqr_plant_score): the realised stage cost and constraint violation of the states a
+        plant visited and the actions it applied, x [B, steps + 1, nx] and u [B, steps, nu] as plant_step_ returns them (the last row
+        of x is not read), under w_plant [B, steps, num_parameter] or, without it, the handle's θ at horizon positions 0 .. steps − 1.
+        To be called while the handle still holds the plan the steps were taken under. Reads the handle; changes none of its state.
+        Returns a dict with cost and violation, each [B, steps]; nothing is summed."""
+        x, u = np.ascontiguousarray(x, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+        if u.ndim != 3 or u.shape[0] != self.B or u.shape[2] != self.nu:
+            raise ValueError("u must have shape [B, steps, nu]")
+        steps, _, w_plant = self._plant_arguments(u.shape[1], None, w_plant, u.shape[1])
+        if x.shape != (self.B, steps + 1, self.nx):
+            raise ValueError("x must have shape [B, steps + 1, nx]")
+        out = dict(cost=np.empty((self.B, steps)), violation=np.empty((self.B, steps)))
+        _ffi.check(_ffi.lib().ilqr_plant_score(self._h, steps, _p(w_plant) if w_plant is not None else None, _p(x), _p(u), _p(out["cost"]),
+                                               _p(out["violation"])))
+        return out
+
+    def plant_score_device_(self, steps, d_x_ptr, d_u_ptr, d_cost_ptr, d_violation_ptr=None, d_w_plant_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not given / not wanted); asynchronous on the handle's
+        stream."""
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_plant_score_device(self._h, int(steps), vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_u_ptr), vp(d_cost_ptr),
+                                                      vp(d_violation_ptr)))
+
     def mpc_run_(self, periods, steps=1, x0=None, plant_feedback=False, shift_feedback=False, shift_tail="hold", warm=True, duals_tail="hold",
-                 duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None):
+                 duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None, w_preview=None, score=False):
         """The closed MPC loop, enqueued once and synchronised once (ilqr_mpc_run): for each of `periods` re-solves plant_step_(steps)
         on a plant state that stays on the device, shift_horizon_(steps, x1 = the plant state), and shift_duals_ + solve_warm_ (warm)
         or solve_. x0 [B, nx]: the first plant state (None: x̄_0 of the handle); w_plant [B, periods · steps, num_parameter]. Returns an
         MpcResult with x [B, periods · steps + 1, nx], u [B, periods · steps, nu], log (a dict of [B, periods] arrays with the fields of
-        stats(), per re-solve) and first_nonfinite [B] (−1, or the global plant step after which a state was not finite)."""
+        stats(), per re-solve) and first_nonfinite [B] (−1, or the global plant step after which a state was not finite).
+        w_preview [B, periods · steps, num_parameter]: the parameter rows that enter the horizon, `steps` of them per period, as
+        shift_horizon_'s w_tail (None: the last row held). score=True: plant_score_ of every period's steps, taken before the shift,
+        as cl_cost and cl_violation [B, periods · steps] of the result. Either goes through ilqr_mpc_run_preview."""
         periods = int(periods)
         if periods < 1:
             raise ValueError("periods must be >= 1")
         steps, sigma_x, w_plant = self._plant_arguments(steps, sigma_x, w_plant, periods * int(steps))
+        if w_preview is not None:
+            w_preview = np.ascontiguousarray(w_preview, dtype=np.float64)
+            if self.num_user_parameter > 0 and w_preview.shape != (self.B, periods * steps, self.num_user_parameter):
+                raise ValueError("w_preview must have shape [B, %d, num_parameter]" % (periods * steps))
         for name, val, table in (("shift_tail", shift_tail, self._TAILS), ("duals_tail", duals_tail, self._TAILS), ("duals_penalty", duals_penalty, self._PENALTIES)):
             if val not in table:
                 raise ValueError("%s must be one of %s" % (name, sorted(table)))
@@ -389,10 +423,18 @@ class Solver:
         R = periods * steps
         x, u = np.empty((self.B, R + 1, self.nx)), np.empty((self.B, R, self.nu))
         log, nf = np.empty((self.B, periods, _ffi.MPC_LOG_W)), np.empty(self.B, dtype=np.int32)
-        _ffi.check(_ffi.lib().ilqr_mpc_run(self._h, C.byref(d), _p(x0) if x0 is not None else None, _p(w_plant) if w_plant is not None else None,
-                                           _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32))))
+        cl_cost, cl_violation = (np.empty((self.B, R)), np.empty((self.B, R))) if score else (None, None)
+        if w_preview is None and not score:
+            _ffi.check(_ffi.lib().ilqr_mpc_run(self._h, C.byref(d), _p(x0) if x0 is not None else None, _p(w_plant) if w_plant is not None else None,
+                                               _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32))))
+        else:
+            _ffi.check(_ffi.lib().ilqr_mpc_run_preview(self._h, C.byref(d), _p(x0) if x0 is not None else None,
+                                                       _p(w_plant) if w_plant is not None else None, _p(w_preview) if w_preview is not None else None,
+                                                       _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                       _p(cl_cost) if score else None, _p(cl_violation) if score else None))
         ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
-        return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)}, nf)
+        return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)}, nf,
+                         cl_cost, cl_violation)
 
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""

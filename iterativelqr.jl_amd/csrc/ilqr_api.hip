@@ -99,7 +99,7 @@ enum { POL_X1, POL_W, POL_COST, POL_VIOL, POL_NONFINITE, POL_X, POL_U, POL_STAGE
 enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
 enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
-enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_STAGES };
+enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -161,7 +161,9 @@ struct ilqr_handle {
     // constraint_penalty since the last reset) — after a reset ρ is not a penalty ladder's and a warm solve would be refused
     bool has_duals = false;
     // ilqr_plant_step: the device staging of its host form (the plant state in and out, w_plant, x_out, u_out, first_nonfinite);
-    // ilqr_mpc_run: the plant state, w_plant, the closed-loop trajectory, the log and first_nonfinite of the whole run
+    // ilqr_mpc_run: the plant state, w_plant, the closed-loop trajectory, the log and first_nonfinite of the whole run;
+    // ilqr_mpc_run_preview: w_preview and the realised scores of the run too; ilqr_plant_score: its host form (x, u and w_plant in
+    // the stages of x_out, u_out and w_plant, the two scores in their own)
     Stage plant[PLANT_STAGES];
 };
 
@@ -1260,13 +1262,16 @@ static int shift_check(const ilqr_handle* h, int32_t steps, int32_t tail, int32_
     return ILQR_OK;
 }
 
-// x1, w_tail: null or device pointers on h's device
-static int shift_launch(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
+// x1, w_tail: null or device pointers on h's device. w_tail_ld < 0: the rows of ONE call, [B][steps][nw]; else instance b's rows
+// start at row b · w_tail_ld + w_tail_row0 (the loop's run-long array)
+static int shift_launch(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail,
+                        long long w_tail_ld = -1, long long w_tail_row0 = 0) {
     if (!h->vt->launch_shift) return fail(ILQR_ERR_MODEL, "this model module has no horizon shift kernel");
     ILQR_TRY(resident_inputs(h));
     ilqr::ShiftArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.tail = tail; a.feedback = feedback ? 1 : 0; a.phase = 0;
     a.x1 = x1; a.w_tail = w_tail; a.w_stage = nullptr; a.r_x1 = h->d_x1; a.r_u = h->d_u;
+    a.w_tail_ld = w_tail_ld < 0 ? steps : w_tail_ld; a.w_tail_row0 = w_tail_ld < 0 ? 0 : w_tail_row0;
     if (steps > 0 && h->L.nw > 0) {            // (no selectors here: every parameter column is the user's)
         ILQR_TRY(grow(h, h->shift[SHIFT_W_STAGE], (size_t)h->B * h->L.T * h->L.nw * 8));
         a.w_stage = (double*)h->shift[SHIFT_W_STAGE].p;
@@ -1401,59 +1406,140 @@ int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t se
     return stage_out(h, arrays);
 }
 
-// ---- the closed MPC loop, enqueued once: per period plant step, horizon shift, dual shift, solve, log row
+// ---- the realised stage cost and violation of plant steps (ilqr_device_score.hpp)
+// everything that can be refused without touching the GPU; what needs no handle comes first
+static int score_check(const ilqr_handle* h, int32_t steps, const double* w_plant, const double* x, const double* u, const double* cost,
+                       const char* who) {
+    const std::string me(who);
+    if (steps < 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
+    if (!x) return fail(ILQR_ERR_INVALID, me + ": null x");
+    if (!u) return fail(ILQR_ERR_INVALID, me + ": null u");
+    if (!cost) return fail(ILQR_ERR_INVALID, me + ": null cost");
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (steps > h->L.T - 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
+    if (w_plant && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_plant given, but this model has no parameters (num_parameter == 0)");
+    return ILQR_OK;
+}
+
+// what a score launch takes of the handle; the arrays, their leading dimensions and row offsets are the caller's to fill in
+static ilqr::ScoreArgs score_args(const ilqr_handle* h, int32_t steps) {
+    ilqr::ScoreArgs a = {};
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.n_sel = h->n_sel; a.constrained = h->constrained;
+    return a;
+}
+
+// every pointer a device pointer on h's device (w_plant, violation: or null); the arrays of ONE call: `steps` rows per instance
+// (x: one more)
+static int score_launch(ilqr_handle* h, int32_t steps, const double* w_plant, const double* x, const double* u, double* cost, double* violation) {
+    if (!h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
+    ilqr::ScoreArgs a = score_args(h, steps);
+    a.w = w_plant; a.x = x; a.u = u; a.cost = cost; a.viol = violation;
+    a.w_ld = a.u_ld = a.cost_ld = a.viol_ld = steps; a.x_ld = steps + 1;
+    if (h->vt->launch_plant_score(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant score launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_plant_score_device(ilqr_handle* h, int32_t steps, const double* w_plant, const double* x, const double* u, double* cost, double* violation) {
+    ILQR_TRY(score_check(h, steps, w_plant, x, u, cost, "ilqr_plant_score_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_plant_score");
+    HIP_TRY(hipSetDevice(h->device));
+    return score_launch(h, steps, w_plant, x, u, cost, violation);
+}
+
+int ilqr_plant_score(ilqr_handle* h, int32_t steps, const double* w_plant, const double* x, const double* u, double* cost, double* violation) {
+    ILQR_TRY(score_check(h, steps, w_plant, x, u, cost, "ilqr_plant_score"));
+    const size_t k = (size_t)steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_plant_score(s, steps, at(w_plant, lo * k * nwu), x + lo * (k + 1) * n, u + lo * k * m, cost + lo * k, at(violation, lo * k)); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * k * nwu * 8);
+    const Staged s_x = staged_in(h->plant[PLANT_X_OUT], x, B * (k + 1) * n * 8);
+    const Staged s_u = staged_in(h->plant[PLANT_U_OUT], u, B * k * m * 8);
+    const Staged s_cost = staged_out(h->plant[PLANT_COST], cost, B * k * 8);
+    const Staged s_viol = staged_out(h->plant[PLANT_VIOL], violation, B * k * 8);
+    const auto arrays = {s_w, s_x, s_u, s_cost, s_viol};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(score_launch(h, steps, s_w.dev<const double>(), s_x.dev<const double>(), s_u.dev<const double>(), s_cost.dev<double>(), s_viol.dev<double>()));
+    return stage_out(h, arrays);
+}
+
+// ---- the closed MPC loop, enqueued once: per period plant step, score, horizon shift, dual shift, solve, log row
 static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
 // everything its constituents refuse for these arguments, before any launch
-static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const double* w_plant) {
-    const std::string me("ilqr_mpc_run");
+static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const double* w_plant, const double* w_preview, const double* cl_cost,
+                     const double* cl_violation, const char* who) {
+    const std::string me(who);
     if (!d) return fail(ILQR_ERR_INVALID, me + ": null descriptor");
     if (d->periods < 1) return fail(ILQR_ERR_INVALID, me + ": periods must be >= 1");
+    if (cl_violation && !cl_cost) return fail(ILQR_ERR_INVALID, me + ": cl_violation without cl_cost: the two scores come from one launch");
     ILQR_TRY(plant_check(h, d->steps, d->plant_feedback, d->first_instance, 0, (int64_t)d->periods * (int64_t)(d->steps > 0 ? d->steps : 0),
-                         d->sigma_x, w_plant, "ilqr_mpc_run"));
-    ILQR_TRY(shift_check(h, d->steps, d->shift_tail, d->shift_feedback, nullptr, "ilqr_mpc_run"));
+                         d->sigma_x, w_plant, who));
+    if (w_preview && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_preview given, but this model has no parameters (num_parameter == 0)");
+    ILQR_TRY(shift_check(h, d->steps, d->shift_tail, d->shift_feedback, w_preview, who));
     if (d->warm) {
         if (!h->constrained) return fail(ILQR_ERR_INVALID, me + ": warm on a handle created unconstrained: it has no duals to keep");
-        ILQR_TRY(duals_check(h, d->steps, d->duals_tail, d->duals_penalty, "ilqr_mpc_run"));
+        ILQR_TRY(duals_check(h, d->steps, d->duals_tail, d->duals_penalty, who));
     }
     return ILQR_OK;
 }
 
-int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, double* x_cl, double* u_cl, double* log,
-                 int32_t* first_nonfinite) {
-    ILQR_TRY(mpc_check(h, d, w_plant));
+// ilqr_mpc_run is this with w_preview, cl_cost and cl_violation null: no launch, no buffer and no argument of it changes then
+static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, const double* w_preview, double* x_cl,
+                   double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, const char* who) {
+    ILQR_TRY(mpc_check(h, d, w_plant, w_preview, cl_cost, cl_violation, who));
     const size_t P = (size_t)d->periods, k = (size_t)d->steps, R = P * k, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         ilqr_mpc_desc sd = *d;
         sd.first_instance += (int64_t)lo;
-        return ilqr_mpc_run(s, &sd, at(x0, lo * n), at(w_plant, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
-                            at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo)); }, true);
+        return mpc_run(s, &sd, at(x0, lo * n), at(w_plant, lo * R * nwu), at(w_preview, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
+                       at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), who); }, true);
     if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
+    const bool score = cl_cost != nullptr;
+    if (score && !h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
     const Staged s_x = staged_in(h->plant[PLANT_X], x0, B * n * 8);
     const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * R * nwu * 8);
+    const Staged s_preview = staged_in(h->plant[PLANT_W_PREVIEW], w_preview, B * R * nwu * 8);
     const Staged s_x_cl = staged_out(h->plant[PLANT_X_OUT], x_cl, B * (R + 1) * n * 8);
     const Staged s_u_cl = staged_out(h->plant[PLANT_U_OUT], u_cl, B * R * m * 8);
     const Staged s_log = staged_out(h->plant[PLANT_LOG], log, B * P * ILQR_MPC_LOG_W * 8);
     const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
-    const auto arrays = {s_x, s_w, s_x_cl, s_u_cl, s_log, s_nonfinite};
-    // Every buffer of the run exists before its first launch — the plant state also without an x0, and what the shift would allocate
-    // in its first call — so that nothing between the first plant launch and the synchronise at the end waits for the device.
+    const Staged s_cost = staged_out(h->plant[PLANT_COST], cl_cost, B * R * 8);
+    const Staged s_viol = staged_out(h->plant[PLANT_VIOL], cl_violation, B * R * 8);
+    const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol};
+    // Every buffer of the run exists before its first launch — the plant state also without an x0, what the shift would allocate
+    // in its first call, and the closed-loop trajectory the score reads even when the caller does not ask for it — so that nothing
+    // between the first plant launch and the synchronise at the end waits for the device.
     ILQR_TRY(grow(h, h->plant[PLANT_X], B * n * 8));
     ILQR_TRY(resident_inputs(h));
     if (h->L.nw > 0) ILQR_TRY(grow(h, h->shift[SHIFT_W_STAGE], B * (size_t)h->L.T * (size_t)h->L.nw * 8));
+    if (score) {
+        ILQR_TRY(grow(h, h->plant[PLANT_X_OUT], B * (R + 1) * n * 8));
+        ILQR_TRY(grow(h, h->plant[PLANT_U_OUT], B * R * m * 8));
+    }
     ILQR_TRY(stage_in(h, arrays));
     double* xp = (double*)h->plant[PLANT_X].p;
+    double* d_x_cl = score ? (double*)h->plant[PLANT_X_OUT].p : s_x_cl.dev<double>();
+    double* d_u_cl = score ? (double*)h->plant[PLANT_U_OUT].p : s_u_cl.dev<double>();
     if (!x0) HIP_TRY(hipMemcpy2DAsync(xp, n * 8, h->ws + h->L.xb, (size_t)h->L.stride * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
     if (s_nonfinite.bytes) HIP_TRY(hipMemsetAsync(s_nonfinite.st->p, 0xff, B * 4, h->stream));       // -1: the plant kernel keeps the first mark
     for (int32_t p = 0; p < d->periods; ++p) {
         ilqr::PlantArgs a = plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, d->sigma_x);
-        a.w = s_w.dev<const double>(); a.x = xp; a.x_out = s_x_cl.dev<double>(); a.u_out = s_u_cl.dev<double>(); a.nonfinite = s_nonfinite.dev<int32_t>();
+        a.w = s_w.dev<const double>(); a.x = xp; a.x_out = d_x_cl; a.u_out = d_u_cl; a.nonfinite = s_nonfinite.dev<int32_t>();
         a.nf_global = 1;
         a.w_ld = (long long)R; a.x_ld = (long long)R + 1; a.u_ld = (long long)R;                     // rows p·k .. of the run's arrays
         a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
         if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
-        ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, xp, nullptr));
+        if (score) {                               // before the shift: it overwrites the θ rows 0 .. k−1 the plant ran under
+            ilqr::ScoreArgs q = score_args(h, d->steps);
+            q.w = a.w; q.x = d_x_cl; q.u = d_u_cl; q.cost = s_cost.dev<double>(); q.viol = s_viol.dev<double>();
+            q.w_ld = q.u_ld = q.cost_ld = q.viol_ld = (long long)R; q.x_ld = (long long)R + 1;
+            q.w_row0 = q.x_row0 = q.u_row0 = q.cost_row0 = q.viol_row0 = a.x_row0;
+            if (h->vt->launch_plant_score(&q, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant score launch failed");
+        }
+        ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, xp, s_preview.dev<const double>(), (long long)R, a.x_row0));
         if (d->warm) ILQR_TRY(ilqr_shift_duals_device(h, d->steps, d->duals_tail, d->duals_penalty));
         ILQR_TRY(d->warm ? ilqr_solve_warm(h) : ilqr_solve(h));
         if (s_log.bytes) {
@@ -1462,6 +1548,16 @@ int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const
         }
     }
     return stage_out(h, arrays);               // the one synchronise of the run
+}
+
+int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, double* x_cl, double* u_cl, double* log,
+                 int32_t* first_nonfinite) {
+    return mpc_run(h, d, x0, w_plant, nullptr, x_cl, u_cl, log, first_nonfinite, nullptr, nullptr, "ilqr_mpc_run");
+}
+
+int ilqr_mpc_run_preview(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, const double* w_preview, double* x_cl,
+                         double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation) {
+    return mpc_run(h, d, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, "ilqr_mpc_run_preview");
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

@@ -2330,10 +2330,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_shift.hpp"
 #include "ilqr_device_duals.hpp"
 #include "ilqr_device_plant.hpp"
+#include "ilqr_device_score.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 17   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 18   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2368,6 +2369,9 @@ extern "C" struct ilqr_model_vtable {
     // only (ilqr_device_plant.hpp). launch_mpc_log: the nine scalars of ilqr_stats of every instance into one row of the loop's log
     int (*launch_plant)(const ilqr::PlantArgs* a, void* stream);
     int (*launch_mpc_log)(const ilqr::PlantArgs* a, void* stream);
+    // the realised stage cost and violation of plant steps, one lane per (instance, step); reads the workspace only
+    // (ilqr_device_score.hpp)
+    int (*launch_plant_score)(const ilqr::ScoreArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2429,7 +2433,7 @@ struct ModelModule {
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
                                              &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>, &launch_shift_duals<M>,
-                                             &launch_plant<M>, &launch_mpc_log<M>};
+                                             &launch_plant<M>, &launch_mpc_log<M>, &launch_plant_score<M>};
         return &vt;
     }
 };

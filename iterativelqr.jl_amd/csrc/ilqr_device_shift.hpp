@@ -32,10 +32,11 @@ struct ShiftArgs {
     int feedback;            // closed loop: the copy kernel leaves u'_t, t < N − k, to the feedback kernel
     int phase;               // shift_copy_kernel: 0 = x1', u', θ' -> staging; 1 = staging -> θ
     const double* x1;        // null, or [B][nx]
-    const double* w_tail;    // null, or [B][steps][nw]
+    const double* w_tail;    // null, or rows of nw doubles: row (b · w_tail_ld + w_tail_row0 + j), j = 0 .. steps-1
     double* w_stage;         // null (θ stays), or [B][T][nw]
     double* r_x1;            // the handle's resident inputs: [B][nx]
     double* r_u;             //                               [B][T-1][nu]
+    long long w_tail_ld, w_tail_row0;   // ilqr_shift_horizon: steps, 0; ilqr_mpc_run_preview: the run's P·k rows, p·k
 };
 
 enum { SHIFT_COPY_THREADS = 128 };
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(SHIFT_COPY_THREADS) void shift_copy_kernel(ShiftArg
     if (a.w_stage) {
         double* st = a.w_stage + (size_t)b * (size_t)(T * nw);
         const int kept = (T - k) * nw;                     // rows that have a source k steps later
-        const double* wt = a.w_tail ? a.w_tail + (size_t)b * (size_t)(k * nw) : nullptr;
+        const double* wt = a.w_tail ? a.w_tail + ((size_t)b * (size_t)a.w_tail_ld + (size_t)a.w_tail_row0) * (size_t)nw : nullptr;
         for (int e = tid; e < T * nw; e += SHIFT_COPY_THREADS)
             st[e] = e < kept ? g[L.w + e + k * nw] : (wt ? wt[e - kept] : g[L.w + (T - 1) * nw + e % nw]);
     }

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 import Libdl
@@ -283,6 +283,69 @@ function mpc_run!(s::Solver; periods::Integer, steps::Integer = 1, plant_feedbac
                     s.handle, d, x0 === nothing ? nul : x0, w_plant === nothing ? nul : w_plant, x, u, log, nf))
     end
     return x, u, log, nf
+end
+
+# The score of plant steps on the device (ilqr_plant_score): the realised stage cost and constraint violation of the states a plant
+# visited and the actions it applied, x :: (nx, steps + 1, B) and u :: (nu, steps, B) as plant_step! returns them, under w_plant or
+# the handle's θ at horizon positions 1 .. steps. To be called while the handle still holds the plan the steps were taken under.
+# Reads the handle. Returns (cost :: (steps, B), violation :: (steps, B)); nothing is summed.
+function plant_score!(s::Solver, x::Array{Float64,3}, u::Array{Float64,3}; w_plant::Union{Nothing,Array{Float64,3}} = nothing)
+    steps = size(u, 2)
+    @assert 1 <= steps <= s.T - 1 && size(x) == (s.nx, steps + 1, s.B) && size(u) == (s.nu, steps, s.B)
+    @assert w_plant === nothing || (size(w_plant, 2) == steps && size(w_plant, 3) == s.B)
+    cost = Matrix{Float64}(undef, steps, s.B)
+    violation = Matrix{Float64}(undef, steps, s.B)
+    check(ccall((:ilqr_plant_score, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, Int32(steps), w_plant === nothing ? Ptr{Float64}(C_NULL) : w_plant, x, u, cost, violation))
+    return cost, violation
+end
+
+# The same with raw device pointers on the handle's device (C_NULL: not given / not wanted); asynchronous on the handle's stream.
+function plant_score_device!(s::Solver, steps::Integer, d_x::Ptr{Float64}, d_u::Ptr{Float64}, d_cost::Ptr{Float64};
+                             d_violation::Ptr{Float64} = Ptr{Float64}(C_NULL), d_w_plant::Ptr{Float64} = Ptr{Float64}(C_NULL))
+    check(ccall((:ilqr_plant_score_device, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, Int32(steps), d_w_plant, d_x, d_u, d_cost, d_violation))
+    return nothing
+end
+
+# mpc_run! following a previewed parameter stream, and scored (ilqr_mpc_run_preview): w_preview :: (nw, periods·steps, B) are the
+# parameter rows that enter the horizon, `steps` of them per period; score = true adds the realised stage cost and violation of every
+# plant step, each :: (periods·steps, B). Returns (x, u, log, first_nonfinite, cl_cost, cl_violation), the last two `nothing` without
+# score. (The symbol is looked up by hand: the descriptor travels as Ref{MpcDesc}.)
+function mpc_run_preview!(s::Solver; periods::Integer, steps::Integer = 1, plant_feedback::Bool = false, shift_feedback::Bool = false,
+                          shift_tail::Symbol = :hold, warm::Bool = true, duals_tail::Symbol = :hold, duals_penalty::Symbol = :keep,
+                          seed::Integer = 0, first_instance::Integer = 0, sigma_x::Union{Nothing,Vector{Float64}} = nothing,
+                          x0::Union{Nothing,Matrix{Float64}} = nothing, w_plant::Union{Nothing,Array{Float64,3}} = nothing,
+                          w_preview::Union{Nothing,Array{Float64,3}} = nothing, score::Bool = false)
+    @assert periods >= 1 && 1 <= steps <= s.T - 1
+    @assert sigma_x === nothing || length(sigma_x) == s.nx
+    @assert x0 === nothing || size(x0) == (s.nx, s.B)
+    R = periods * steps
+    @assert w_plant === nothing || (size(w_plant, 2) == R && size(w_plant, 3) == s.B)
+    @assert w_preview === nothing || (size(w_preview, 2) == R && size(w_preview, 3) == s.B)
+    nul = Ptr{Float64}(C_NULL)
+    x = Array{Float64,3}(undef, s.nx, R + 1, s.B)
+    u = Array{Float64,3}(undef, s.nu, R, s.B)
+    log = Array{Float64,3}(undef, 9, periods, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    cl_cost = score ? Matrix{Float64}(undef, R, s.B) : nothing
+    cl_violation = score ? Matrix{Float64}(undef, R, s.B) : nothing
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    sig = sigma_x === nothing ? Float64[] : sigma_x
+    GC.@preserve sig begin
+        d = MpcDesc(Int32(periods), Int32(steps), Int32(plant_feedback ? 1 : 0), Int32(shift_feedback ? 1 : 0),
+                    Int32(shift_tail === :hold ? 0 : 1), Int32(warm ? 1 : 0), Int32(duals_tail === :hold ? 0 : 1),
+                    Int32(duals_penalty === :keep ? 0 : 1), UInt64(seed), Int64(first_instance),
+                    sigma_x === nothing ? nul : pointer(sig))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_mpc_run_preview)
+        check(ccall(fn, Cint, (Ptr{Cvoid}, Ref{MpcDesc}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, d, x0 === nothing ? nul : x0, w_plant === nothing ? nul : w_plant, w_preview === nothing ? nul : w_preview,
+                    x, u, log, nf, score ? cl_cost : nul, score ? cl_violation : nul))
+    end
+    return x, u, log, nf, cl_cost, cl_violation
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
