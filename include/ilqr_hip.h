@@ -362,6 +362,83 @@ int ilqr_mpc_run_preview(ilqr_handle* h, const ilqr_mpc_desc* d,
                          double* cl_cost,           /* NULL, or [B][P*k]: realised stage cost of every plant step */
                          double* cl_violation);     /* NULL, or [B][P*k]: realised stage violation; needs cl_cost */
 
+/* The seam between plant and controller: actuator limits, measurement noise and a compute delay.
+ *
+ * ilqr_plant_step_limited is ilqr_plant_step with an actuator that saturates. After the action is formed, feedback included, and
+ * before it is recorded in u_out and handed to the dynamics, every component r is limited by plain comparisons:
+ *     u ← u < u_min[r] ? u_min[r] : (u > u_max[r] ? u_max[r] : u)
+ * so a NaN action stays NaN (first_nonfinite marks the state it produces) and a limit of ∓Inf leaves every finite action bit for
+ * bit. A null u_min (u_max) is no limit on that side; with both null the call is ilqr_plant_step, bit for bit. u_out records the
+ * action APPLIED, so ilqr_plant_score of it judges what the actuator did. saturated[b]: the number of (step, component) pairs with
+ * u < u_min[r] or u > u_max[r]. Refused (ILQR_ERR_INVALID) without touching the GPU: everything ilqr_plant_step refuses, a NaN
+ * limit, u_min[r] > u_max[r], limits on a model with nu > 16 (they travel by value, as sigma_x does). Host and device form as
+ * ilqr_plant_step's: u_min and u_max are HOST arrays in both. */
+int ilqr_plant_step_limited(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                            const double* sigma_x,     /* HOST, NULL or [nx], finite, >= 0 */
+                            const double* u_min,       /* HOST, NULL or [nu]: no NaN; -Inf = no limit */
+                            const double* u_max,       /* HOST, NULL or [nu]: no NaN, >= u_min; +Inf = no limit */
+                            const double* w_plant,     /* NULL, or [B][steps][nw_user] */
+                            double* x,                 /* [B][nx], in: plant state, out: plant state after k steps */
+                            double* x_out,             /* NULL, or [B][steps+1][nx]  (row 0 = the input state) */
+                            double* u_out,             /* NULL, or [B][steps][nu]    (the actions applied) */
+                            int32_t* first_nonfinite,  /* NULL, or [B] */
+                            int32_t* saturated);       /* NULL, or [B] */
+int ilqr_plant_step_limited_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                                   const double* sigma_x, const double* u_min, const double* u_max, const double* d_w_plant, double* d_x,
+                                   double* d_x_out, double* d_u_out, int32_t* d_first_nonfinite, int32_t* d_saturated);
+
+/* What a controller is given of a plant state: for every instance b and state component j
+ *     y[b][j] = x[b][j]                                                                       (sigma_y NULL, or sigma_y[j] == 0)
+ *     y[b][j] = x[b][j] + sigma_y[j] · z(seed, first_instance + b, 5 + j / 16, step, j % 16)  (product and sum rounded separately)
+ * z as in ilqr_plant_step; `step` is the number of plant steps taken when the measurement is made. The process noise of
+ * ilqr_plant_step draws from candidate fields 1 .. 4 and the measurement from 5 .. 8, so under one seed the two streams are disjoint:
+ * ilqr_candidate_noise(seed, first_instance, B, 9, step + 1, 16, z) is the host twin (rows 5 .., step `step`). The call reads
+ * nothing of the handle but its dimensions, device and stream. Refused (ILQR_ERR_INVALID) without touching the GPU: a null handle, x
+ * or y, step < 0 or >= 2^20, first_instance < 0 or first_instance + batch > 2^23, a negative or non-finite sigma_y entry, nx > 64.
+ * Host form: works on a sharded handle, synchronous. Device form: x and y device pointers (they may be the same array),
+ * asynchronous on the handle's stream; refused on a sharded handle. */
+int ilqr_plant_measure(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step,
+                       const double* sigma_y,          /* HOST, NULL or [nx], finite, >= 0 */
+                       const double* x,                /* [B][nx] */
+                       double* y);                     /* [B][nx] */
+int ilqr_plant_measure_device(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, const double* sigma_y, const double* d_x,
+                              double* d_y);
+
+/* ilqr_mpc_run_preview with the seam in the loop. The plant state xp stays the truth; the controller works from its own view xc of it.
+ * Per period p, with k = steps:
+ *   delay == 1, before the plant launch: xc = ilqr_plant_measure_device(step = p·k, sigma_y, xp), then xc moves on by k steps under
+ *       the head of the plan in flight — ilqr_plant_step_limited_device with the same feedback flag and limits, no sigma_x, no
+ *       w_plant, no outputs: the controller's model prediction of time (p+1)·k from a measurement one period old, which is when a
+ *       solve that takes one period has to start
+ *   1.  ilqr_plant_step_limited_device on xp as in ilqr_mpc_run, with u_min, u_max; saturated accumulates over the run
+ *   delay == 0, after the plant launch: xc = ilqr_plant_measure_device(step = (p+1)·k, sigma_y, xp)
+ *   y_cl[b][p] = xc, what the controller was given; 1b .. 5 as before, the shift with x1 = xc.
+ * x_cl, u_cl, cl_cost and cl_violation report the true plant and the actions applied. Still one enqueue and one synchronise, every
+ * buffer grown before the first launch. With io NULL — or all its pointers NULL and delay 0 — and y_cl and saturated NULL the call is
+ * ilqr_mpc_run_preview: no launch, buffer or argument differs. Refused (ILQR_ERR_INVALID) before any launch: everything
+ * ilqr_mpc_run_preview, ilqr_plant_step_limited and ilqr_plant_measure refuse for these arguments (a measurement step >= 2^20:
+ * with delay 0 the last one is taken at P·k), delay not 0 or 1. Works on a sharded handle. */
+typedef struct {
+    const double* u_min;      /* HOST, NULL or [nu] */
+    const double* u_max;      /* HOST, NULL or [nu] */
+    const double* sigma_y;    /* HOST, NULL or [nx] */
+    int32_t delay;            /* 0: the re-solve starts from a measurement of the state it is applied from; 1: from a one-period prediction */
+    int32_t reserved;
+} ilqr_plant_io;
+int ilqr_mpc_run_io(ilqr_handle* h, const ilqr_mpc_desc* d,
+                    const ilqr_plant_io* io,   /* NULL: none */
+                    const double* x0,          /* NULL (= x̄_0 of the handle), or [B][nx] */
+                    const double* w_plant,     /* NULL, or [B][P*k][nw_user] */
+                    const double* w_preview,   /* NULL, or [B][P*k][nw_user] */
+                    double* x_cl,              /* NULL, or [B][P*k+1][nx] */
+                    double* u_cl,              /* NULL, or [B][P*k][nu]: the actions applied */
+                    double* log,               /* NULL, or [B][P][ILQR_MPC_LOG_W] */
+                    int32_t* first_nonfinite,  /* NULL, or [B]: global plant step index, or -1 */
+                    double* cl_cost,           /* NULL, or [B][P*k] */
+                    double* cl_violation,      /* NULL, or [B][P*k]; needs cl_cost */
+                    double* y_cl,              /* NULL, or [B][P][nx]: what the controller was given per period */
+                    int32_t* saturated);       /* NULL, or [B] */
+
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):
  * the reference functions they run are listed per id. */
 enum {

@@ -52,6 +52,15 @@ class ilqr_mpc_desc(C.Structure):
 
 
 MpcDesc = ilqr_mpc_desc
+
+
+class ilqr_plant_io(C.Structure):
+    """The seam between plant and controller of ilqr_mpc_run_io, under the header's own name: actuator limits, measurement noise and a
+    compute delay of 0 or 1 periods. The three vectors are host arrays the caller keeps alive over the call."""
+    _fields_ = [("u_min", c_double_p), ("u_max", c_double_p), ("sigma_y", c_double_p), ("delay", C.c_int32), ("reserved", C.c_int32)]
+
+
+PlantIO = ilqr_plant_io
 MPC_LOG_W = 9
 MPC_LOG_COLUMNS = ("objective", "gradient_norm", "max_violation", "step_size", "iterations", "outer_iterations", "status", "potrf_info",
                    "rollouts")
@@ -152,6 +161,14 @@ SYMBOLS = {
     "ilqr_plant_score_device": (C.c_int, [C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "ilqr_mpc_run_preview": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                        C.POINTER(C.c_int32), c_double_p, c_double_p]),
+    "ilqr_plant_step_limited": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ilqr_plant_step_limited_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p,
+                                                 c_double_p] + [C.c_void_p] * 6),
+    "ilqr_plant_measure": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p, c_double_p]),
+    "ilqr_plant_measure_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, c_double_p, C.c_void_p, C.c_void_p]),
+    "ilqr_mpc_run_io": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                  c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32)]),
     "ilqr_solve":(C.c_int, [C.c_void_p]),
     "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),

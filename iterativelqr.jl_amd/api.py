@@ -32,14 +32,38 @@ def _p(a):
     return a.ctypes.data_as(_ffi.c_double_p)
 
 
+def _limits(nu, u_min, u_max):
+    """the actuator's limits as contiguous float64 vectors of nu entries (None stays None)"""
+    out = []
+    for name, v in (("u_min", u_min), ("u_max", u_max)):
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=np.float64)
+            if v.shape != (nu,):
+                raise ValueError("%s must have nu entries" % name)
+        out.append(v)
+    return out
+
+
+def _sigma_y(nx, sigma_y):
+    if sigma_y is None:
+        return None
+    sigma_y = np.ascontiguousarray(sigma_y, dtype=np.float64)
+    if sigma_y.shape != (nx,):
+        raise ValueError("sigma_y must have nx entries")
+    return sigma_y
+
+
 class MpcResult:
     """What Solver.mpc_run_ returns: the closed-loop states x and actions u, the per-period log and first_nonfinite; with score=True
-    the realised stage cost and violation of every plant step, cl_cost and cl_violation [B, periods · steps] (None otherwise)."""
-    __slots__ = ("x", "u", "log", "first_nonfinite", "cl_cost", "cl_violation")
+    the realised stage cost and violation of every plant step, cl_cost and cl_violation [B, periods · steps] (None otherwise); with
+    limits, measurement noise or a delay what the controller was given per period, y_cl [B, periods, nx], and the number of (step,
+    component) pairs the actuator's limits changed, saturated [B] (None otherwise)."""
+    __slots__ = ("x", "u", "log", "first_nonfinite", "cl_cost", "cl_violation", "y_cl", "saturated")
 
-    def __init__(self, x, u, log, first_nonfinite, cl_cost=None, cl_violation=None):
+    def __init__(self, x, u, log, first_nonfinite, cl_cost=None, cl_violation=None, y_cl=None, saturated=None):
         self.x, self.u, self.log, self.first_nonfinite = x, u, log, first_nonfinite
         self.cl_cost, self.cl_violation = cl_cost, cl_violation
+        self.y_cl, self.saturated = y_cl, saturated
 
 
 MODEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -338,33 +362,72 @@ class Solver:
                 raise ValueError("w_plant must have shape [B, %d, num_parameter]" % rows)
         return steps, sigma_x, w_plant
 
-    def plant_step_(self, x, steps=1, feedback=False, sigma_x=None, seed=0, first_instance=0, step0=0, w_plant=None):
+    def plant_step_(self, x, steps=1, feedback=False, sigma_x=None, seed=0, first_instance=0, step0=0, w_plant=None, u_min=None, u_max=None):
         """The plant of a closed MPC loop on the device (ilqr_plant_step): the plant states x [B, nx] move on by `steps` control
         periods under the head of the handle's plan, u_i = ū_i, or with feedback=True ū_i + K_i (x − x̄_i); x ← f(x, u_i, w_i), then
         x_j += sigma_x[j] · z with z = candidate_noise(seed, first_instance + b, 1 + j // 16, step0 + i, j % 16). w_plant [B, steps,
         num_parameter]: the plant's own parameters (None: the handle's). Reads the handle; changes none of its state. Returns a dict
         with x [B, steps + 1, nx] (row 0 the input states, the last row the new plant states), u [B, steps, nu] and first_nonfinite [B]
-        (−1, or the first step after which a state component is not finite)."""
+        (−1, or the first step after which a state component is not finite). u_min, u_max [nu] (either may be None): the actuator's
+        limits (ilqr_plant_step_limited) — the action, feedback included, is clamped into them before it is applied and recorded in
+        u, and the dict gains saturated [B], the number of (step, component) pairs the clamp changed."""
         steps, sigma_x, w_plant = self._plant_arguments(steps, sigma_x, w_plant, int(steps))
+        u_min, u_max = _limits(self.nu, u_min, u_max)
         x = np.array(x, dtype=np.float64, order="C")
         if x.shape != (self.B, self.nx):
             raise ValueError("x must have shape [B, nx]")
         out = dict(x=np.empty((self.B, steps + 1, self.nx)), u=np.empty((self.B, steps, self.nu)), first_nonfinite=np.empty(self.B, dtype=np.int32))
+        if u_min is not None or u_max is not None:
+            out["saturated"] = np.empty(self.B, dtype=np.int32)
+            _ffi.check(_ffi.lib().ilqr_plant_step_limited(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
+                                                          _p(sigma_x) if sigma_x is not None else None, _p(u_min) if u_min is not None else None,
+                                                          _p(u_max) if u_max is not None else None, _p(w_plant) if w_plant is not None else None,
+                                                          _p(x), _p(out["x"]), _p(out["u"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          out["saturated"].ctypes.data_as(C.POINTER(C.c_int32))))
+            return out
         _ffi.check(_ffi.lib().ilqr_plant_step(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
                                               _p(sigma_x) if sigma_x is not None else None, _p(w_plant) if w_plant is not None else None, _p(x),
                                               _p(out["x"]), _p(out["u"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
     def plant_step_device_(self, d_x_ptr, steps=1, feedback=False, sigma_x=None, seed=0, first_instance=0, step0=0, d_w_plant_ptr=None,
-                           d_x_out_ptr=None, d_u_out_ptr=None, d_first_nonfinite_ptr=None):
+                           d_x_out_ptr=None, d_u_out_ptr=None, d_first_nonfinite_ptr=None, u_min=None, u_max=None, d_saturated_ptr=None):
         """The same with raw device pointers on the handle's device (None = not given / not wanted); d_x_ptr [B, nx] is updated in
-        place; sigma_x stays a host array; asynchronous on the handle's stream."""
+        place; sigma_x, u_min and u_max stay host arrays; asynchronous on the handle's stream."""
         steps, sigma_x, _ = self._plant_arguments(steps, sigma_x, None, int(steps))
+        u_min, u_max = _limits(self.nu, u_min, u_max)
         def vp(p):
             return C.c_void_p(p) if p else None
+        if u_min is not None or u_max is not None or d_saturated_ptr:
+            _ffi.check(_ffi.lib().ilqr_plant_step_limited_device(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
+                                                                 _p(sigma_x) if sigma_x is not None else None,
+                                                                 _p(u_min) if u_min is not None else None, _p(u_max) if u_max is not None else None,
+                                                                 vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_x_out_ptr), vp(d_u_out_ptr),
+                                                                 vp(d_first_nonfinite_ptr), vp(d_saturated_ptr)))
+            return
         _ffi.check(_ffi.lib().ilqr_plant_step_device(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
                                                      _p(sigma_x) if sigma_x is not None else None, vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_x_out_ptr),
                                                      vp(d_u_out_ptr), vp(d_first_nonfinite_ptr)))
+
+    def plant_measure_(self, x, step=0, sigma_y=None, seed=0, first_instance=0):
+        """What a controller is given of the plant states x [B, nx] (ilqr_plant_measure): y = x where sigma_y is None or zero, else
+        y_j = x_j + sigma_y[j] · z with z = candidate_noise(seed, first_instance + b, 5 + j // 16, step, j % 16) — `step` the number of
+        plant steps taken when the measurement is made. Reads nothing of the handle's state. Returns y [B, nx]."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.B, self.nx):
+            raise ValueError("x must have shape [B, nx]")
+        sigma_y = _sigma_y(self.nx, sigma_y)
+        y = np.empty((self.B, self.nx))
+        _ffi.check(_ffi.lib().ilqr_plant_measure(self._h, int(seed), int(first_instance), int(step), _p(sigma_y) if sigma_y is not None else None,
+                                                 _p(x), _p(y)))
+        return y
+
+    def plant_measure_device_(self, d_x_ptr, d_y_ptr, step=0, sigma_y=None, seed=0, first_instance=0):
+        """The same with raw device pointers on the handle's device (they may be the same array); sigma_y stays a host array;
+        asynchronous on the handle's stream."""
+        sigma_y = _sigma_y(self.nx, sigma_y)
+        _ffi.check(_ffi.lib().ilqr_plant_measure_device(self._h, int(seed), int(first_instance), int(step),
+                                                        _p(sigma_y) if sigma_y is not None else None, C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr)))
 
     def plant_score_(self, x, u, w_plant=None):
         """The score of plant steps on the device (ilqr_plant_score): the realised stage cost and constraint violation of the states a
@@ -392,7 +455,8 @@ class Solver:
                                                       vp(d_violation_ptr)))
 
     def mpc_run_(self, periods, steps=1, x0=None, plant_feedback=False, shift_feedback=False, shift_tail="hold", warm=True, duals_tail="hold",
-                 duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None, w_preview=None, score=False):
+                 duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None, w_preview=None, score=False, u_min=None, u_max=None,
+                 sigma_y=None, delay=0):
         """The closed MPC loop, enqueued once and synchronised once (ilqr_mpc_run): for each of `periods` re-solves plant_step_(steps)
         on a plant state that stays on the device, shift_horizon_(steps, x1 = the plant state), and shift_duals_ + solve_warm_ (warm)
         or solve_. x0 [B, nx]: the first plant state (None: x̄_0 of the handle); w_plant [B, periods · steps, num_parameter]. Returns an
@@ -400,10 +464,19 @@ class Solver:
         stats(), per re-solve) and first_nonfinite [B] (−1, or the global plant step after which a state was not finite).
         w_preview [B, periods · steps, num_parameter]: the parameter rows that enter the horizon, `steps` of them per period, as
         shift_horizon_'s w_tail (None: the last row held). score=True: plant_score_ of every period's steps, taken before the shift,
-        as cl_cost and cl_violation [B, periods · steps] of the result. Either goes through ilqr_mpc_run_preview."""
+        as cl_cost and cl_violation [B, periods · steps] of the result. Either goes through ilqr_mpc_run_preview.
+        u_min, u_max [nu]: the actuator's limits, as plant_step_'s; sigma_y [nx]: measurement noise, as plant_measure_'s, on the plant
+        state the shift is handed; delay=1: the re-solve is anchored at a one-period model prediction from a measurement one period
+        old (the solve takes a period), instead of at a measurement of the state it is applied from. Any of them goes through
+        ilqr_mpc_run_io, and the result carries y_cl [B, periods, nx], what the controller was given, and saturated [B]."""
         periods = int(periods)
         if periods < 1:
             raise ValueError("periods must be >= 1")
+        if delay not in (0, 1):
+            raise ValueError("delay must be 0 or 1")
+        u_min, u_max = _limits(self.nu, u_min, u_max)
+        sigma_y = _sigma_y(self.nx, sigma_y)
+        io = u_min is not None or u_max is not None or sigma_y is not None or delay == 1
         steps, sigma_x, w_plant = self._plant_arguments(steps, sigma_x, w_plant, periods * int(steps))
         if w_preview is not None:
             w_preview = np.ascontiguousarray(w_preview, dtype=np.float64)
@@ -424,7 +497,16 @@ class Solver:
         x, u = np.empty((self.B, R + 1, self.nx)), np.empty((self.B, R, self.nu))
         log, nf = np.empty((self.B, periods, _ffi.MPC_LOG_W)), np.empty(self.B, dtype=np.int32)
         cl_cost, cl_violation = (np.empty((self.B, R)), np.empty((self.B, R))) if score else (None, None)
-        if w_preview is None and not score:
+        y_cl = saturated = None
+        if io:
+            def nul(a):
+                return _p(a) if a is not None else None
+            pio = _ffi.PlantIO(nul(u_min), nul(u_max), nul(sigma_y), int(delay), 0)
+            y_cl, saturated = np.empty((self.B, periods, self.nx)), np.empty(self.B, dtype=np.int32)
+            _ffi.check(_ffi.lib().ilqr_mpc_run_io(self._h, C.byref(d), C.byref(pio), nul(x0), nul(w_plant), nul(w_preview), _p(x), _p(u), _p(log),
+                                                  nf.ctypes.data_as(C.POINTER(C.c_int32)), nul(cl_cost), nul(cl_violation), _p(y_cl),
+                                                  saturated.ctypes.data_as(C.POINTER(C.c_int32))))
+        elif w_preview is None and not score:
             _ffi.check(_ffi.lib().ilqr_mpc_run(self._h, C.byref(d), _p(x0) if x0 is not None else None, _p(w_plant) if w_plant is not None else None,
                                                _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32))))
         else:
@@ -434,7 +516,7 @@ class Solver:
                                                        _p(cl_cost) if score else None, _p(cl_violation) if score else None))
         ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
         return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)}, nf,
-                         cl_cost, cl_violation)
+                         cl_cost, cl_violation, y_cl, saturated)
 
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""

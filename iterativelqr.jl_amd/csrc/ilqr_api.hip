@@ -99,7 +99,8 @@ enum { POL_X1, POL_W, POL_COST, POL_VIOL, POL_NONFINITE, POL_X, POL_U, POL_STAGE
 enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
 enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
-enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_STAGES };
+enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_SATURATED, PLANT_XC,
+       PLANT_Y, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -163,7 +164,9 @@ struct ilqr_handle {
     // ilqr_plant_step: the device staging of its host form (the plant state in and out, w_plant, x_out, u_out, first_nonfinite);
     // ilqr_mpc_run: the plant state, w_plant, the closed-loop trajectory, the log and first_nonfinite of the whole run;
     // ilqr_mpc_run_preview: w_preview and the realised scores of the run too; ilqr_plant_score: its host form (x, u and w_plant in
-    // the stages of x_out, u_out and w_plant, the two scores in their own)
+    // the stages of x_out, u_out and w_plant, the two scores in their own); ilqr_plant_step_limited: the saturation counts too;
+    // ilqr_plant_measure: x in the stage of the plant state, y in its own; ilqr_mpc_run_io: the controller's state xc, what it was
+    // given per period (y_cl, in the stage of y) and the saturation counts of the run
     Stage plant[PLANT_STAGES];
 };
 
@@ -1336,19 +1339,36 @@ int ilqr_shift_duals(ilqr_handle* h, int32_t steps, int32_t tail, int32_t penalt
 }
 
 // ---- the plant of a closed MPC loop (ilqr_device_plant.hpp): the head of the plan applied to the dynamics from a plant state in HBM
-// everything that can be refused without touching the GPU; what needs no handle comes first
+// a standard deviation vector (sigma_x, sigma_y): finite and >= 0; its first `count` entries
+static int sigma_check(const double* sigma, int count, const std::string& me, const char* name) {
+    for (int j = 0; sigma && j < count; ++j)
+        if (!(sigma[j] >= 0.0) || !std::isfinite(sigma[j])) return fail(ILQR_ERR_INVALID, me + ": " + name + " must be finite and >= 0");
+    return ILQR_OK;
+}
+// the actuator's limits: no NaN, u_min <= u_max; their first `count` entries (a null vector: no limit on that side)
+static int limits_check(const double* u_min, const double* u_max, int count, const std::string& me) {
+    for (int j = 0; j < count; ++j) {
+        if ((u_min && std::isnan(u_min[j])) || (u_max && std::isnan(u_max[j]))) return fail(ILQR_ERR_INVALID, me + ": a limit of the actuator is NaN");
+        if (u_min && u_max && u_min[j] > u_max[j]) return fail(ILQR_ERR_INVALID, me + ": u_min must not exceed u_max");
+    }
+    return ILQR_OK;
+}
+
+// everything that can be refused without touching the GPU; what needs no handle comes first (of a vector: its first entry)
 static int plant_check(const ilqr_handle* h, int32_t steps, int32_t feedback, int64_t first_instance, int64_t step0, int64_t total_steps,
-                       const double* sigma_x, const double* w_plant, const char* who) {
+                       const double* sigma_x, const double* u_min, const double* u_max, const double* w_plant, const char* who) {
     const std::string me(who);
     if (steps < 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
     if (step0 < 0 || step0 + total_steps > ilqr::PLANT_MAX_STEPS) return fail(ILQR_ERR_INVALID, me + ": step0 >= 0 and no plant step index beyond 2^20 (the noise key's bit fields)");
     if (first_instance < 0 || first_instance >= ilqr::PLANT_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance must lie in 0 .. 2^23 - 1");
-    if (sigma_x && (!(sigma_x[0] >= 0.0) || !std::isfinite(sigma_x[0]))) return fail(ILQR_ERR_INVALID, me + ": sigma_x must be finite and >= 0");
+    ILQR_TRY(sigma_check(sigma_x, 1, me, "sigma_x"));
+    ILQR_TRY(limits_check(u_min, u_max, 1, me));
     if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
     if (steps > h->L.T - 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
     if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
-    for (int j = 0; sigma_x && j < h->L.nx; ++j)
-        if (!(sigma_x[j] >= 0.0) || !std::isfinite(sigma_x[j])) return fail(ILQR_ERR_INVALID, me + ": sigma_x must be finite and >= 0");
+    ILQR_TRY(sigma_check(sigma_x, h->L.nx, me, "sigma_x"));
+    if ((u_min || u_max) && h->L.nu > ilqr::PLANT_MAX_NU) return fail(ILQR_ERR_INVALID, me + ": limits on more than 16 action components");
+    ILQR_TRY(limits_check(u_min, u_max, h->L.nu, me));
     if (first_instance + (int64_t)h->B > ilqr::PLANT_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance + batch must not exceed 2^23");
     if (w_plant && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_plant given, but this model has no parameters (num_parameter == 0)");
     if (feedback && !every_shard_holds(h, &ilqr_handle::has_policy))
@@ -1358,40 +1378,64 @@ static int plant_check(const ilqr_handle* h, int32_t steps, int32_t feedback, in
 
 // what a plant launch takes of the handle and of the call; the arrays are the caller's to fill in
 static ilqr::PlantArgs plant_args(const ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
-                                  const double* sigma_x) {
+                                  const double* sigma_x, const double* u_min = nullptr, const double* u_max = nullptr) {
     ilqr::PlantArgs a = {};
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.feedback = feedback ? 1 : 0; a.n_sel = h->n_sel; a.step0 = step0;
     a.noise = sigma_x != nullptr; a.nf_global = 0; a.seed = seed; a.b0 = first_instance;
     for (int j = 0; sigma_x && j < h->L.nx; ++j) a.sigma[j] = sigma_x[j];      // by value: the caller's array may go away at once
+    a.clamp = (u_min || u_max) ? 1 : 0;
+    for (int j = 0; a.clamp && j < h->L.nu; ++j) {
+        a.u_lo[j] = u_min ? u_min[j] : -HUGE_VAL;
+        a.u_hi[j] = u_max ? u_max[j] : HUGE_VAL;
+    }
     return a;
 }
 
 // every pointer null or a device pointer on h's device; the arrays of ONE call: `steps` rows per instance (x_out: one more)
-static int plant_launch(ilqr_handle* h, ilqr::PlantArgs a, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
+static int plant_launch(ilqr_handle* h, ilqr::PlantArgs a, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite,
+                        int32_t* saturated) {
     if (!h->vt->launch_plant) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
-    a.w = w_plant; a.x = x; a.x_out = x_out; a.u_out = u_out; a.nonfinite = first_nonfinite;
+    a.w = w_plant; a.x = x; a.x_out = x_out; a.u_out = u_out; a.nonfinite = first_nonfinite; a.saturated = saturated;
     a.w_ld = a.steps; a.x_ld = a.steps + 1; a.u_ld = a.steps;
     if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
     return ILQR_OK;
 }
 
-int ilqr_plant_step_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
-                           const double* sigma_x, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
-    if (!x) return fail(ILQR_ERR_INVALID, "ilqr_plant_step_device: null x");
-    ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, w_plant, "ilqr_plant_step_device"));
-    if (SHARDED(h)) return refuse_sharded("ilqr_plant_step");
+// ilqr_plant_step_device is this with u_min, u_max and saturated null: no buffer and no argument of the launch changes then
+static int plant_step_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                             const double* sigma_x, const double* u_min, const double* u_max, const double* w_plant, double* x, double* x_out,
+                             double* u_out, int32_t* first_nonfinite, int32_t* saturated, const char* who, const char* host_form) {
+    if (!x) return fail(ILQR_ERR_INVALID, std::string(who) + ": null x");
+    ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, u_min, u_max, w_plant, who));
+    if (SHARDED(h)) return refuse_sharded(host_form);
     HIP_TRY(hipSetDevice(h->device));
-    return plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x), w_plant, x, x_out, u_out, first_nonfinite);
+    return plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x, u_min, u_max), w_plant, x, x_out, u_out,
+                        first_nonfinite, saturated);
 }
 
-int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
-                    const double* sigma_x, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
-    if (!x) return fail(ILQR_ERR_INVALID, "ilqr_plant_step: null x");
-    ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, w_plant, "ilqr_plant_step"));
+int ilqr_plant_step_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                           const double* sigma_x, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
+    return plant_step_device(h, steps, feedback, seed, first_instance, step0, sigma_x, nullptr, nullptr, w_plant, x, x_out, u_out, first_nonfinite,
+                             nullptr, "ilqr_plant_step_device", "ilqr_plant_step");
+}
+
+int ilqr_plant_step_limited_device(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                                   const double* sigma_x, const double* u_min, const double* u_max, const double* w_plant, double* x,
+                                   double* x_out, double* u_out, int32_t* first_nonfinite, int32_t* saturated) {
+    return plant_step_device(h, steps, feedback, seed, first_instance, step0, sigma_x, u_min, u_max, w_plant, x, x_out, u_out, first_nonfinite,
+                             saturated, "ilqr_plant_step_limited_device", "ilqr_plant_step_limited");
+}
+
+// ilqr_plant_step is this with u_min, u_max and saturated null
+static int plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0, const double* sigma_x,
+                      const double* u_min, const double* u_max, const double* w_plant, double* x, double* x_out, double* u_out,
+                      int32_t* first_nonfinite, int32_t* saturated, const char* who) {
+    if (!x) return fail(ILQR_ERR_INVALID, std::string(who) + ": null x");
+    ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, u_min, u_max, w_plant, who));
     const size_t k = (size_t)steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_plant_step(s, steps, feedback, seed, first_instance + (int64_t)lo, step0, sigma_x, at(w_plant, lo * k * nwu), x + lo * n,
-                               at(x_out, lo * (k + 1) * n), at(u_out, lo * k * m), at(first_nonfinite, lo)); }, true);
+        return plant_step(s, steps, feedback, seed, first_instance + (int64_t)lo, step0, sigma_x, u_min, u_max, at(w_plant, lo * k * nwu), x + lo * n,
+                          at(x_out, lo * (k + 1) * n), at(u_out, lo * k * m), at(first_nonfinite, lo), at(saturated, lo), who); }, true);
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
     const Staged s_x = {&h->plant[PLANT_X], x, x, B * n * 8};                // the plant state goes in and comes back
@@ -1399,10 +1443,71 @@ int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t se
     const Staged s_x_out = staged_out(h->plant[PLANT_X_OUT], x_out, B * (k + 1) * n * 8);
     const Staged s_u_out = staged_out(h->plant[PLANT_U_OUT], u_out, B * k * m * 8);
     const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
-    const auto arrays = {s_x, s_w, s_x_out, s_u_out, s_nonfinite};
+    const Staged s_saturated = staged_out(h->plant[PLANT_SATURATED], saturated, B * 4);
+    const auto arrays = {s_x, s_w, s_x_out, s_u_out, s_nonfinite, s_saturated};
     ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x), s_w.dev<const double>(), s_x.dev<double>(),
-                          s_x_out.dev<double>(), s_u_out.dev<double>(), s_nonfinite.dev<int32_t>()));
+    ILQR_TRY(plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x, u_min, u_max), s_w.dev<const double>(),
+                          s_x.dev<double>(), s_x_out.dev<double>(), s_u_out.dev<double>(), s_nonfinite.dev<int32_t>(), s_saturated.dev<int32_t>()));
+    return stage_out(h, arrays);
+}
+
+int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                    const double* sigma_x, const double* w_plant, double* x, double* x_out, double* u_out, int32_t* first_nonfinite) {
+    return plant_step(h, steps, feedback, seed, first_instance, step0, sigma_x, nullptr, nullptr, w_plant, x, x_out, u_out, first_nonfinite, nullptr,
+                      "ilqr_plant_step");
+}
+
+int ilqr_plant_step_limited(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
+                            const double* sigma_x, const double* u_min, const double* u_max, const double* w_plant, double* x, double* x_out,
+                            double* u_out, int32_t* first_nonfinite, int32_t* saturated) {
+    return plant_step(h, steps, feedback, seed, first_instance, step0, sigma_x, u_min, u_max, w_plant, x, x_out, u_out, first_nonfinite, saturated,
+                      "ilqr_plant_step_limited");
+}
+
+// ---- what the controller is given of a plant state (plant_measure_kernel, ilqr_device_plant.hpp)
+// everything that can be refused without touching the GPU; what needs no handle comes first (of sigma_y: its first entry)
+static int measure_check(const ilqr_handle* h, int64_t first_instance, int64_t step, const double* sigma_y, const char* who) {
+    const std::string me(who);
+    if (step < 0 || step >= ilqr::PLANT_MAX_STEPS) return fail(ILQR_ERR_INVALID, me + ": the measurement step must lie in 0 .. 2^20 - 1 (the noise key's bit fields)");
+    if (first_instance < 0 || first_instance >= ilqr::PLANT_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance must lie in 0 .. 2^23 - 1");
+    ILQR_TRY(sigma_check(sigma_y, 1, me, "sigma_y"));
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
+    ILQR_TRY(sigma_check(sigma_y, h->L.nx, me, "sigma_y"));
+    if (first_instance + (int64_t)h->B > ilqr::PLANT_MAX_INSTANCES) return fail(ILQR_ERR_INVALID, me + ": first_instance + batch must not exceed 2^23");
+    return ILQR_OK;
+}
+
+// x, y: device pointers on h's device, [B][nx] each (they may be the same array)
+static int measure_launch(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, const double* sigma_y, const double* x, double* y) {
+    if (!h->vt->launch_plant_measure) return fail(ILQR_ERR_MODEL, "this model module has no measurement kernel");
+    ilqr::MeasureArgs a = {};
+    a.B = h->B; a.noise = sigma_y != nullptr; a.step = step; a.seed = seed; a.b0 = first_instance; a.x = x; a.y = y;
+    for (int j = 0; sigma_y && j < h->L.nx; ++j) a.sigma[j] = sigma_y[j];      // by value: the caller's array may go away at once
+    if (h->vt->launch_plant_measure(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "measurement launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_plant_measure_device(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, const double* sigma_y, const double* x, double* y) {
+    if (!x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_device: null x or y");
+    ILQR_TRY(measure_check(h, first_instance, step, sigma_y, "ilqr_plant_measure_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_plant_measure");
+    HIP_TRY(hipSetDevice(h->device));
+    return measure_launch(h, seed, first_instance, step, sigma_y, x, y);
+}
+
+int ilqr_plant_measure(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, const double* sigma_y, const double* x, double* y) {
+    if (!x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure: null x or y");
+    ILQR_TRY(measure_check(h, first_instance, step, sigma_y, "ilqr_plant_measure"));
+    const size_t n = (size_t)h->L.nx;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_plant_measure(s, seed, first_instance + (int64_t)lo, step, sigma_y, x + lo * n, y + lo * n); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const Staged s_x = staged_in(h->plant[PLANT_X], x, (size_t)h->B * n * 8);
+    const Staged s_y = staged_out(h->plant[PLANT_Y], y, (size_t)h->B * n * 8);
+    const auto arrays = {s_x, s_y};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(measure_launch(h, seed, first_instance, step, sigma_y, s_x.dev<const double>(), s_y.dev<double>()));
     return stage_out(h, arrays);
 }
 
@@ -1467,14 +1572,29 @@ int ilqr_plant_score(ilqr_handle* h, int32_t steps, const double* w_plant, const
 // ---- the closed MPC loop, enqueued once: per period plant step, score, horizon shift, dual shift, solve, log row
 static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
 // everything its constituents refuse for these arguments, before any launch
-static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const double* w_plant, const double* w_preview, const double* cl_cost,
-                     const double* cl_violation, const char* who) {
+// The seam between plant and controller is in use: limits, measurement noise, a delay, or one of the two outputs that report on it.
+// Otherwise the loop hands the shift the plant state itself: no launch, no buffer and no argument of it differs from ilqr_mpc_run's.
+static bool mpc_measured(const ilqr_plant_io* io, const double* y_cl, const int32_t* saturated) {
+    return (io && (io->u_min || io->u_max || io->sigma_y || io->delay)) || y_cl || saturated;
+}
+// measured: the run goes through the measurement slot (mpc_measured)
+static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, bool measured, const double* w_plant,
+                     const double* w_preview, const double* cl_cost, const double* cl_violation, const char* who) {
     const std::string me(who);
     if (!d) return fail(ILQR_ERR_INVALID, me + ": null descriptor");
     if (d->periods < 1) return fail(ILQR_ERR_INVALID, me + ": periods must be >= 1");
     if (cl_violation && !cl_cost) return fail(ILQR_ERR_INVALID, me + ": cl_violation without cl_cost: the two scores come from one launch");
-    ILQR_TRY(plant_check(h, d->steps, d->plant_feedback, d->first_instance, 0, (int64_t)d->periods * (int64_t)(d->steps > 0 ? d->steps : 0),
-                         d->sigma_x, w_plant, who));
+    if (io && io->delay != 0 && io->delay != 1) return fail(ILQR_ERR_INVALID, me + ": delay must be 0 or 1");
+    const int64_t run_steps = (int64_t)d->periods * (int64_t)(d->steps > 0 ? d->steps : 0);
+    // the last measurement: of the state after the run's last plant step (delay 0), before its last period (delay 1)
+    const int64_t last_measured = io && io->delay ? run_steps - (d->steps > 0 ? d->steps : 0) : run_steps;
+    if (measured) {                                // what needs no handle, as plant_check orders it
+        if (last_measured >= ilqr::PLANT_MAX_STEPS) return fail(ILQR_ERR_INVALID, me + ": the measurement step must lie in 0 .. 2^20 - 1 (the noise key's bit fields)");
+        ILQR_TRY(sigma_check(io ? io->sigma_y : nullptr, 1, me, "sigma_y"));
+    }
+    ILQR_TRY(plant_check(h, d->steps, d->plant_feedback, d->first_instance, 0, run_steps, d->sigma_x, io ? io->u_min : nullptr,
+                         io ? io->u_max : nullptr, w_plant, who));
+    if (measured) ILQR_TRY(measure_check(h, d->first_instance, last_measured, io ? io->sigma_y : nullptr, who));
     if (w_preview && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_preview given, but this model has no parameters (num_parameter == 0)");
     ILQR_TRY(shift_check(h, d->steps, d->shift_tail, d->shift_feedback, w_preview, who));
     if (d->warm) {
@@ -1484,19 +1604,24 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const double*
     return ILQR_OK;
 }
 
-// ilqr_mpc_run is this with w_preview, cl_cost and cl_violation null: no launch, no buffer and no argument of it changes then
-static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, const double* w_preview, double* x_cl,
-                   double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, const char* who) {
-    ILQR_TRY(mpc_check(h, d, w_plant, w_preview, cl_cost, cl_violation, who));
+// ilqr_mpc_run is this with w_preview, cl_cost and cl_violation null and nothing measured (mpc_measured); ilqr_mpc_run_preview with
+// nothing measured: no launch, no buffer and no argument of it changes then
+static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const double* x0, const double* w_plant, const double* w_preview,
+                   double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
+                   int32_t* saturated, const char* who) {
+    const bool measured = mpc_measured(io, y_cl, saturated);
+    ILQR_TRY(mpc_check(h, d, io, measured, w_plant, w_preview, cl_cost, cl_violation, who));
     const size_t P = (size_t)d->periods, k = (size_t)d->steps, R = P * k, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         ilqr_mpc_desc sd = *d;
         sd.first_instance += (int64_t)lo;
-        return mpc_run(s, &sd, at(x0, lo * n), at(w_plant, lo * R * nwu), at(w_preview, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
-                       at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), who); }, true);
+        return mpc_run(s, &sd, io, at(x0, lo * n), at(w_plant, lo * R * nwu), at(w_preview, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
+                       at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), at(y_cl, lo * P * n),
+                       at(saturated, lo), who); }, true);
     if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
     const bool score = cl_cost != nullptr;
     if (score && !h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
+    if (measured && !h->vt->launch_plant_measure) return fail(ILQR_ERR_MODEL, "this model module has no measurement kernel");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
     const Staged s_x = staged_in(h->plant[PLANT_X], x0, B * n * 8);
@@ -1508,10 +1633,12 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, con
     const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
     const Staged s_cost = staged_out(h->plant[PLANT_COST], cl_cost, B * R * 8);
     const Staged s_viol = staged_out(h->plant[PLANT_VIOL], cl_violation, B * R * 8);
-    const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol};
+    const Staged s_y_cl = staged_out(h->plant[PLANT_Y], y_cl, B * P * n * 8);
+    const Staged s_saturated = staged_out(h->plant[PLANT_SATURATED], saturated, B * 4);
+    const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol, s_y_cl, s_saturated};
     // Every buffer of the run exists before its first launch — the plant state also without an x0, what the shift would allocate
-    // in its first call, and the closed-loop trajectory the score reads even when the caller does not ask for it — so that nothing
-    // between the first plant launch and the synchronise at the end waits for the device.
+    // in its first call, the closed-loop trajectory the score reads even when the caller does not ask for it, and the controller's
+    // state of a measured run — so that nothing between the first plant launch and the synchronise at the end waits for the device.
     ILQR_TRY(grow(h, h->plant[PLANT_X], B * n * 8));
     ILQR_TRY(resident_inputs(h));
     if (h->L.nw > 0) ILQR_TRY(grow(h, h->shift[SHIFT_W_STAGE], B * (size_t)h->L.T * (size_t)h->L.nw * 8));
@@ -1519,19 +1646,37 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, con
         ILQR_TRY(grow(h, h->plant[PLANT_X_OUT], B * (R + 1) * n * 8));
         ILQR_TRY(grow(h, h->plant[PLANT_U_OUT], B * R * m * 8));
     }
+    if (measured) ILQR_TRY(grow(h, h->plant[PLANT_XC], B * n * 8));
     ILQR_TRY(stage_in(h, arrays));
     double* xp = (double*)h->plant[PLANT_X].p;
+    double* xc = measured ? (double*)h->plant[PLANT_XC].p : xp;        // what the shift is handed: the controller's view of the plant state
     double* d_x_cl = score ? (double*)h->plant[PLANT_X_OUT].p : s_x_cl.dev<double>();
     double* d_u_cl = score ? (double*)h->plant[PLANT_U_OUT].p : s_u_cl.dev<double>();
+    const double* u_min = io ? io->u_min : nullptr;
+    const double* u_max = io ? io->u_max : nullptr;
+    const double* sigma_y = io ? io->sigma_y : nullptr;
+    const bool delayed = io && io->delay == 1;
     if (!x0) HIP_TRY(hipMemcpy2DAsync(xp, n * 8, h->ws + h->L.xb, (size_t)h->L.stride * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
     if (s_nonfinite.bytes) HIP_TRY(hipMemsetAsync(s_nonfinite.st->p, 0xff, B * 4, h->stream));       // -1: the plant kernel keeps the first mark
+    if (s_saturated.bytes) HIP_TRY(hipMemsetAsync(s_saturated.st->p, 0, B * 4, h->stream));          // the plant kernel adds to it
     for (int32_t p = 0; p < d->periods; ++p) {
-        ilqr::PlantArgs a = plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, d->sigma_x);
+        if (delayed) {
+            // the solve of this period started one period ago: from a measurement of the state at p·k, moved on by the controller's
+            // own model under the plan in flight — same feedback and limits, no process noise, the handle's parameters, no outputs
+            ILQR_TRY(measure_launch(h, d->seed, d->first_instance, p * d->steps, sigma_y, xp, xc));
+            ILQR_TRY(plant_launch(h, plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, nullptr, u_min, u_max),
+                                  nullptr, xc, nullptr, nullptr, nullptr, nullptr));
+        }
+        ilqr::PlantArgs a = plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, d->sigma_x, u_min, u_max);
         a.w = s_w.dev<const double>(); a.x = xp; a.x_out = d_x_cl; a.u_out = d_u_cl; a.nonfinite = s_nonfinite.dev<int32_t>();
+        a.saturated = s_saturated.dev<int32_t>();
         a.nf_global = 1;
         a.w_ld = (long long)R; a.x_ld = (long long)R + 1; a.u_ld = (long long)R;                     // rows p·k .. of the run's arrays
         a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
         if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
+        if (measured && !delayed) ILQR_TRY(measure_launch(h, d->seed, d->first_instance, (p + 1) * d->steps, sigma_y, xp, xc));
+        if (s_y_cl.bytes)                          // row p of y_cl: what the controller is given
+            HIP_TRY(hipMemcpy2DAsync(s_y_cl.dev<double>() + (size_t)p * n, P * n * 8, xc, n * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));
         if (score) {                               // before the shift: it overwrites the θ rows 0 .. k−1 the plant ran under
             ilqr::ScoreArgs q = score_args(h, d->steps);
             q.w = a.w; q.x = d_x_cl; q.u = d_u_cl; q.cost = s_cost.dev<double>(); q.viol = s_viol.dev<double>();
@@ -1539,7 +1684,7 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, con
             q.w_row0 = q.x_row0 = q.u_row0 = q.cost_row0 = q.viol_row0 = a.x_row0;
             if (h->vt->launch_plant_score(&q, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant score launch failed");
         }
-        ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, xp, s_preview.dev<const double>(), (long long)R, a.x_row0));
+        ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, xc, s_preview.dev<const double>(), (long long)R, a.x_row0));
         if (d->warm) ILQR_TRY(ilqr_shift_duals_device(h, d->steps, d->duals_tail, d->duals_penalty));
         ILQR_TRY(d->warm ? ilqr_solve_warm(h) : ilqr_solve(h));
         if (s_log.bytes) {
@@ -1552,12 +1697,19 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, con
 
 int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, double* x_cl, double* u_cl, double* log,
                  int32_t* first_nonfinite) {
-    return mpc_run(h, d, x0, w_plant, nullptr, x_cl, u_cl, log, first_nonfinite, nullptr, nullptr, "ilqr_mpc_run");
+    return mpc_run(h, d, nullptr, x0, w_plant, nullptr, x_cl, u_cl, log, first_nonfinite, nullptr, nullptr, nullptr, nullptr, "ilqr_mpc_run");
 }
 
 int ilqr_mpc_run_preview(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, const double* w_preview, double* x_cl,
                          double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation) {
-    return mpc_run(h, d, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, "ilqr_mpc_run_preview");
+    return mpc_run(h, d, nullptr, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, nullptr, nullptr,
+                   "ilqr_mpc_run_preview");
+}
+
+int ilqr_mpc_run_io(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const double* x0, const double* w_plant, const double* w_preview,
+                    double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
+                    int32_t* saturated) {
+    return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_io");
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 import Libdl
@@ -346,6 +346,101 @@ function mpc_run_preview!(s::Solver; periods::Integer, steps::Integer = 1, plant
                     x, u, log, nf, score ? cl_cost : nul, score ? cl_violation : nul))
     end
     return x, u, log, nf, cl_cost, cl_violation
+end
+
+# plant_step! with an actuator that saturates (ilqr_plant_step_limited): the action, feedback included, is clamped into
+# [u_min, u_max] (either may be nothing: no limit on that side) before it is applied and recorded. Returns (x_out, u_out,
+# first_nonfinite, saturated :: B — the (step, component) pairs the clamp changed); x is updated in place.
+function plant_step_limited!(s::Solver, x::Matrix{Float64}; steps::Integer = 1, feedback::Bool = false, seed::Integer = 0,
+                             first_instance::Integer = 0, step0::Integer = 0, sigma_x::Union{Nothing,Vector{Float64}} = nothing,
+                             u_min::Union{Nothing,Vector{Float64}} = nothing, u_max::Union{Nothing,Vector{Float64}} = nothing,
+                             w_plant::Union{Nothing,Array{Float64,3}} = nothing)
+    @assert 1 <= steps <= s.T - 1 && size(x) == (s.nx, s.B)
+    @assert sigma_x === nothing || length(sigma_x) == s.nx
+    @assert (u_min === nothing || length(u_min) == s.nu) && (u_max === nothing || length(u_max) == s.nu)
+    @assert w_plant === nothing || (size(w_plant, 2) == steps && size(w_plant, 3) == s.B)
+    nul = Ptr{Float64}(C_NULL)
+    x_out = Array{Float64,3}(undef, s.nx, steps + 1, s.B)
+    u_out = Array{Float64,3}(undef, s.nu, steps, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    saturated = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_plant_step_limited, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Int32}),
+                s.handle, Int32(steps), Int32(feedback ? 1 : 0), UInt64(seed), Int64(first_instance), Int32(step0),
+                sigma_x === nothing ? nul : sigma_x, u_min === nothing ? nul : u_min, u_max === nothing ? nul : u_max,
+                w_plant === nothing ? nul : w_plant, x, x_out, u_out, nf, saturated))
+    return x_out, u_out, nf, saturated
+end
+
+# What a controller is given of the plant states x :: (nx, B) (ilqr_plant_measure): y = x where sigma_y is nothing or zero, else
+# y_j = x_j + sigma_y[j] · z with z the noise of candidate_noise at candidate 5 + j ÷ 16, step `step`, component j % 16; `step` is
+# the number of plant steps taken when the measurement is made. Returns y :: (nx, B).
+function plant_measure!(s::Solver, x::Matrix{Float64}; step::Integer = 0, seed::Integer = 0, first_instance::Integer = 0,
+                        sigma_y::Union{Nothing,Vector{Float64}} = nothing)
+    @assert size(x) == (s.nx, s.B) && (sigma_y === nothing || length(sigma_y) == s.nx)
+    y = Matrix{Float64}(undef, s.nx, s.B)
+    check(ccall((:ilqr_plant_measure, LIB[]), Cint,
+                (Ptr{Cvoid}, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, UInt64(seed), Int64(first_instance), Int32(step), sigma_y === nothing ? Ptr{Float64}(C_NULL) : sigma_y, x, y))
+    return y
+end
+
+# ilqr_plant_io, field for field
+struct PlantIO
+    u_min::Ptr{Float64}
+    u_max::Ptr{Float64}
+    sigma_y::Ptr{Float64}
+    delay::Int32
+    reserved::Int32
+end
+
+# mpc_run_preview! with the seam between plant and controller in the loop (ilqr_mpc_run_io): actuator limits u_min, u_max,
+# measurement noise sigma_y on the state the shift is handed, and delay = 1 — the re-solve is anchored at a one-period model
+# prediction from a measurement one period old. Returns (x, u, log, first_nonfinite, cl_cost, cl_violation, y_cl :: (nx, periods, B),
+# saturated :: B). (The symbol is looked up by hand: the descriptors travel as Ref{MpcDesc}, Ref{PlantIO}.)
+function mpc_run_io!(s::Solver; periods::Integer, steps::Integer = 1, plant_feedback::Bool = false, shift_feedback::Bool = false,
+                     shift_tail::Symbol = :hold, warm::Bool = true, duals_tail::Symbol = :hold, duals_penalty::Symbol = :keep,
+                     seed::Integer = 0, first_instance::Integer = 0, sigma_x::Union{Nothing,Vector{Float64}} = nothing,
+                     x0::Union{Nothing,Matrix{Float64}} = nothing, w_plant::Union{Nothing,Array{Float64,3}} = nothing,
+                     w_preview::Union{Nothing,Array{Float64,3}} = nothing, score::Bool = false,
+                     u_min::Union{Nothing,Vector{Float64}} = nothing, u_max::Union{Nothing,Vector{Float64}} = nothing,
+                     sigma_y::Union{Nothing,Vector{Float64}} = nothing, delay::Integer = 0)
+    @assert periods >= 1 && 1 <= steps <= s.T - 1 && (delay == 0 || delay == 1)
+    @assert sigma_x === nothing || length(sigma_x) == s.nx
+    @assert sigma_y === nothing || length(sigma_y) == s.nx
+    @assert (u_min === nothing || length(u_min) == s.nu) && (u_max === nothing || length(u_max) == s.nu)
+    @assert x0 === nothing || size(x0) == (s.nx, s.B)
+    R = periods * steps
+    @assert w_plant === nothing || (size(w_plant, 2) == R && size(w_plant, 3) == s.B)
+    @assert w_preview === nothing || (size(w_preview, 2) == R && size(w_preview, 3) == s.B)
+    nul = Ptr{Float64}(C_NULL)
+    x = Array{Float64,3}(undef, s.nx, R + 1, s.B)
+    u = Array{Float64,3}(undef, s.nu, R, s.B)
+    log = Array{Float64,3}(undef, 9, periods, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    cl_cost = score ? Matrix{Float64}(undef, R, s.B) : nothing
+    cl_violation = score ? Matrix{Float64}(undef, R, s.B) : nothing
+    y_cl = Array{Float64,3}(undef, s.nx, periods, s.B)
+    saturated = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    sig = sigma_x === nothing ? Float64[] : sigma_x
+    lo = u_min === nothing ? Float64[] : u_min
+    hi = u_max === nothing ? Float64[] : u_max
+    sy = sigma_y === nothing ? Float64[] : sigma_y
+    GC.@preserve sig lo hi sy begin
+        d = MpcDesc(Int32(periods), Int32(steps), Int32(plant_feedback ? 1 : 0), Int32(shift_feedback ? 1 : 0),
+                    Int32(shift_tail === :hold ? 0 : 1), Int32(warm ? 1 : 0), Int32(duals_tail === :hold ? 0 : 1),
+                    Int32(duals_penalty === :keep ? 0 : 1), UInt64(seed), Int64(first_instance),
+                    sigma_x === nothing ? nul : pointer(sig))
+        io = PlantIO(u_min === nothing ? nul : pointer(lo), u_max === nothing ? nul : pointer(hi),
+                     sigma_y === nothing ? nul : pointer(sy), Int32(delay), Int32(0))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_mpc_run_io)
+        check(ccall(fn, Cint, (Ptr{Cvoid}, Ref{MpcDesc}, Ref{PlantIO}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                    s.handle, d, io, x0 === nothing ? nul : x0, w_plant === nothing ? nul : w_plant, w_preview === nothing ? nul : w_preview,
+                    x, u, log, nf, score ? cl_cost : nul, score ? cl_violation : nul, y_cl, saturated))
+    end
+    return x, u, log, nf, cl_cost, cl_violation, y_cl, saturated
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
