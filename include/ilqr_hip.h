@@ -439,6 +439,85 @@ int ilqr_mpc_run_io(ilqr_handle* h, const ilqr_mpc_desc* d,
                     double* y_cl,              /* NULL, or [B][P][nx]: what the controller was given per period */
                     int32_t* saturated);       /* NULL, or [B] */
 
+/* An extended Kalman filter between the plant's sensor and the controller, batched on the device. Per instance b: the estimate
+ * x̂ [nx]; its covariance P [nx][nx], row-major, symmetric, both triangles stored; q [nx] the process noise variances (diagonal Q);
+ * r [nx] the measurement noise variances (diagonal R); measured [nx] a 0/1 mask (NULL: every component is measured).
+ *
+ * ilqr_estimate_predict, the time update over k = steps control periods under the head of the handle's plan, for i = 0 .. k−1:
+ *     u_i = what ilqr_plant_step_limited forms from the state it is handed, here x̂: ū_i, or with feedback ū_i + K_i (x̂ − x̄_i),
+ *           then the limits
+ *     w_i = θ_i as the handle holds it (the filter knows the controller's model only: there is no w_plant); the selector columns
+ *           of a lowered problem follow ilqr_plant_step's rule
+ *     F   = ∂f/∂x (x̂, u_i, w_i), the model's own dynamics state Jacobian — the one the solver linearises with — taken before the
+ *           state moves
+ *     x̂  ← f(x̂, u_i, w_i), no noise: bit for bit the state ilqr_plant_step_limited_device gives from the same input with the same
+ *           flag and limits and no sigma_x
+ *     P  ← F P Fᵀ + diag(q): the elements with row >= column are computed and each is copied to its mirror, so the stored matrix
+ *           is exactly symmetric. The summation order inside the two products is the kernel's; it depends on the model's sizes
+ *           alone: the same instance gives the same bits in any batch.
+ * ilqr_estimate_update, the measurement update with y [nx]: for j = 0 .. nx−1 in increasing order where measured[j], on the x̂ and P
+ * the previous j left:
+ *     ν_j = y_j − x̂_j,  s_j = P_jj + r_j. If s_j is not a finite number > 0 the component is skipped and first_bad[b] becomes j
+ *           (the first such j is kept; −1 if there is none)
+ *     g = P[:, j] / s_j;  x̂ ← x̂ + g · ν_j;  P_ab ← P_ab − g_a · P_jb for a >= b, from the column and row as they were before this j,
+ *           then mirrored
+ *     nis[b] = Σ_j ν_j² / s_j over the components that were updated; innovation[b][j] = ν_j, or 0 where the component was not
+ *           measured or was skipped
+ * R being diagonal, the sequence equals the batch update with S = H P Hᵀ + R, and nis equals νᵀ S⁻¹ ν.
+ * Both calls read the handle and change none of its state. Refused (ILQR_ERR_INVALID) before any launch: everything
+ * ilqr_plant_step_limited refuses for the same arguments; a null xhat, P, y or r; a negative or non-finite q entry; an r entry that
+ * is not finite and > 0 at a measured component; a mask entry other than 0 or 1; nx > 64. Host forms: work on a sharded handle,
+ * synchronous. Device forms: xhat, P, y, innovation, nis and first_bad device pointers, asynchronous on the handle's stream;
+ * refused on a sharded handle. */
+int ilqr_estimate_predict(ilqr_handle* h, int32_t steps, int32_t feedback,
+                          const double* u_min,            /* HOST, NULL or [nu]: ilqr_plant_step_limited's rules */
+                          const double* u_max,            /* HOST, NULL or [nu] */
+                          const double* q,                /* HOST, NULL (= 0) or [nx], finite, >= 0 */
+                          double* xhat,                   /* [B][nx] in / out */
+                          double* P);                     /* [B][nx][nx] in / out */
+int ilqr_estimate_predict_device(ilqr_handle* h, int32_t steps, int32_t feedback, const double* u_min, const double* u_max, const double* q,
+                                 double* d_xhat, double* d_P);
+int ilqr_estimate_update(ilqr_handle* h,
+                         const int32_t* measured,         /* HOST, NULL or [nx] of 0 / 1 */
+                         const double* r,                 /* HOST [nx]; finite and > 0 where measured */
+                         const double* y,                 /* [B][nx]; unmeasured components are not read */
+                         double* xhat,                    /* [B][nx] in / out */
+                         double* P,                       /* [B][nx][nx] in / out */
+                         double* innovation,              /* NULL, or [B][nx] */
+                         double* nis,                     /* NULL, or [B] */
+                         int32_t* first_bad);             /* NULL, or [B] */
+int ilqr_estimate_update_device(ilqr_handle* h, const int32_t* measured, const double* r, const double* d_y, double* d_xhat, double* d_P,
+                                double* d_innovation, double* d_nis, int32_t* d_first_bad);
+
+/* ilqr_mpc_run_io with the filter between sensor and controller. Per period p, with k = steps:
+ *   delay == 0:  1. the plant step on xp;  2. y = ilqr_plant_measure_device(step = (p+1)·k, sigma_y, xp);
+ *                3. ilqr_estimate_predict_device(k, plant_feedback, the limits, q) under the plan in flight;
+ *                4. ilqr_estimate_update_device(y);  5. xc = x̂
+ *   delay == 1, before the plant launch:  1. y = measure(step = p·k);  2. the update;  3. the prediction of k steps under the plan in
+ *                flight;  4. xc = x̂, which now stands at time (p+1)·k;  5. then the plant step
+ * and the loop goes on as ilqr_mpc_run_io's: the shift with x1 = xc, and so on. y_cl[b][p] is the measurement taken, every component as
+ * ilqr_plant_measure writes it; xhat_cl[b][p] = xc; pdiag_cl[b][p] the diagonal of P at that moment; nis_cl[b][p] that period's nis. P
+ * holds P0 on entry and the last covariance on return. Still one enqueue and one synchronise, every buffer grown before the first
+ * launch. With est NULL the call is ilqr_mpc_run_io: no launch, buffer or argument differs. Refused (ILQR_ERR_INVALID) before any
+ * launch: everything ilqr_mpc_run_io and the two estimator calls refuse; est with P NULL; xhat0, P, xhat_cl, pdiag_cl or nis_cl
+ * without est. Works on a sharded handle. */
+typedef struct {
+    const int32_t* measured;   /* HOST, NULL or [nx] */
+    const double* q;           /* HOST, NULL or [nx] */
+    const double* r;           /* HOST, [nx] */
+} ilqr_estimator;
+int ilqr_mpc_run_est(ilqr_handle* h, const ilqr_mpc_desc* d,
+                     const ilqr_plant_io* io,   /* NULL: none */
+                     const ilqr_estimator* est, /* NULL: ilqr_mpc_run_io */
+                     const double* x0,          /* NULL (= x̄_0 of the handle), or [B][nx] */
+                     const double* xhat0,       /* NULL (= the first plant state), or [B][nx] */
+                     double* P,                 /* [B][nx][nx] in: P0, out: the last covariance */
+                     const double* w_plant, const double* w_preview, double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite,
+                     double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated,       /* as ilqr_mpc_run_io's */
+                     double* xhat_cl,           /* NULL, or [B][P][nx] */
+                     double* pdiag_cl,          /* NULL, or [B][P][nx] */
+                     double* nis_cl);           /* NULL, or [B][P] */
+
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):
  * the reference functions they run are listed per id. */
 enum {

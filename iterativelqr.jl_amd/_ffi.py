@@ -61,6 +61,15 @@ class ilqr_plant_io(C.Structure):
 
 
 PlantIO = ilqr_plant_io
+
+
+class ilqr_estimator(C.Structure):
+    """ilqr_estimator: the filter of ilqr_mpc_run_est — the 0/1 mask of the measured components and the diagonals of Q and R (named
+    as in the header: the static check compares pointer targets by name)."""
+    _fields_ = [("measured", C.POINTER(C.c_int32)), ("q", c_double_p), ("r", c_double_p)]
+
+
+Estimator = ilqr_estimator
 MPC_LOG_W = 9
 MPC_LOG_COLUMNS = ("objective", "gradient_norm", "max_violation", "step_size", "iterations", "outer_iterations", "status", "potrf_info",
                    "rollouts")
@@ -169,6 +178,14 @@ SYMBOLS = {
     "ilqr_plant_measure_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, c_double_p, C.c_void_p, C.c_void_p]),
     "ilqr_mpc_run_io": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32)]),
+    "ilqr_estimate_predict": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "ilqr_estimate_predict_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, C.c_void_p, C.c_void_p]),
+    "ilqr_estimate_update": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                       C.POINTER(C.c_int32)]),
+    "ilqr_estimate_update_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), c_double_p] + [C.c_void_p] * 6),
+    "ilqr_mpc_run_est": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), C.POINTER(Estimator), c_double_p, c_double_p, c_double_p,
+                                   c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
+                                   c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
     "ilqr_solve":(C.c_int, [C.c_void_p]),
     "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),

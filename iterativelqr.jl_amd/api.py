@@ -53,17 +53,39 @@ def _sigma_y(nx, sigma_y):
     return sigma_y
 
 
+def _variances(nx, measured, q, r):
+    """the filter's mask (int32) and variance vectors (float64) of nx entries each (None stays None)"""
+    if measured is not None:
+        measured = np.ascontiguousarray(measured, dtype=np.int32)
+        if measured.shape != (nx,):
+            raise ValueError("measured must have nx entries")
+    out = [measured]
+    for name, v in (("q", q), ("r", r)):
+        if v is not None:
+            v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (nx,)))
+        out.append(v)
+    return out
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32)) if a is not None else None
+
+
 class MpcResult:
     """What Solver.mpc_run_ returns: the closed-loop states x and actions u, the per-period log and first_nonfinite; with score=True
     the realised stage cost and violation of every plant step, cl_cost and cl_violation [B, periods · steps] (None otherwise); with
     limits, measurement noise or a delay what the controller was given per period, y_cl [B, periods, nx], and the number of (step,
-    component) pairs the actuator's limits changed, saturated [B] (None otherwise)."""
-    __slots__ = ("x", "u", "log", "first_nonfinite", "cl_cost", "cl_violation", "y_cl", "saturated")
+    component) pairs the actuator's limits changed, saturated [B] (None otherwise); with an estimator the estimate the controller
+    was anchored at per period, xhat [B, periods, nx], the diagonal of its covariance at that moment, pdiag [B, periods, nx], the
+    period's normalised innovation squared, nis [B, periods], and the last covariance P [B, nx, nx] (None otherwise)."""
+    __slots__ = ("x", "u", "log", "first_nonfinite", "cl_cost", "cl_violation", "y_cl", "saturated", "xhat", "pdiag", "nis", "P")
 
-    def __init__(self, x, u, log, first_nonfinite, cl_cost=None, cl_violation=None, y_cl=None, saturated=None):
+    def __init__(self, x, u, log, first_nonfinite, cl_cost=None, cl_violation=None, y_cl=None, saturated=None, xhat=None, pdiag=None, nis=None,
+                 P=None):
         self.x, self.u, self.log, self.first_nonfinite = x, u, log, first_nonfinite
         self.cl_cost, self.cl_violation = cl_cost, cl_violation
         self.y_cl, self.saturated = y_cl, saturated
+        self.xhat, self.pdiag, self.nis, self.P = xhat, pdiag, nis, P
 
 
 MODEL_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -429,6 +451,66 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_plant_measure_device(self._h, int(seed), int(first_instance), int(step),
                                                         _p(sigma_y) if sigma_y is not None else None, C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr)))
 
+    def _estimate_arrays(self, xhat, P):
+        xhat, P = np.array(xhat, dtype=np.float64, order="C"), np.array(P, dtype=np.float64, order="C")
+        if xhat.shape != (self.B, self.nx):
+            raise ValueError("xhat must have shape [B, nx]")
+        if P.shape != (self.B, self.nx, self.nx):
+            raise ValueError("P must have shape [B, nx, nx]")
+        return xhat, P
+
+    def estimate_predict_(self, xhat, P, steps=1, feedback=False, u_min=None, u_max=None, q=None):
+        """The time update of the extended Kalman filter on the device (ilqr_estimate_predict): the estimates xhat [B, nx] move on by
+        `steps` control periods under the head of the handle's plan exactly as plant_step_ moves a state without noise (feedback,
+        u_min, u_max as there), and per step P ← F P Fᵀ + diag(q) with F the model's dynamics state Jacobian at the estimate before it
+        moves. P [B, nx, nx] symmetric; q [nx] (or a scalar, None = 0). Reads the handle; changes none of its state. Returns (xhat, P),
+        new arrays."""
+        steps, _, _ = self._plant_arguments(steps, None, None, int(steps))
+        u_min, u_max = _limits(self.nu, u_min, u_max)
+        _, q, _ = _variances(self.nx, None, q, None)
+        xhat, P = self._estimate_arrays(xhat, P)
+        nul = lambda a: _p(a) if a is not None else None
+        _ffi.check(_ffi.lib().ilqr_estimate_predict(self._h, steps, 1 if feedback else 0, nul(u_min), nul(u_max), nul(q), _p(xhat), _p(P)))
+        return xhat, P
+
+    def estimate_predict_device_(self, d_xhat_ptr, d_P_ptr, steps=1, feedback=False, u_min=None, u_max=None, q=None):
+        """The same with raw device pointers on the handle's device, updated in place; u_min, u_max and q stay host arrays;
+        asynchronous on the handle's stream."""
+        steps, _, _ = self._plant_arguments(steps, None, None, int(steps))
+        u_min, u_max = _limits(self.nu, u_min, u_max)
+        _, q, _ = _variances(self.nx, None, q, None)
+        nul = lambda a: _p(a) if a is not None else None
+        _ffi.check(_ffi.lib().ilqr_estimate_predict_device(self._h, steps, 1 if feedback else 0, nul(u_min), nul(u_max), nul(q),
+                                                           C.c_void_p(d_xhat_ptr), C.c_void_p(d_P_ptr)))
+
+    def estimate_update_(self, xhat, P, y, r, measured=None):
+        """The measurement update of the filter on the device (ilqr_estimate_update): the components j of y [B, nx] with measured[j]
+        (None: all) are taken in one after the other, ν = y_j − x̂_j, s = P_jj + r[j], g = P[:, j] / s, x̂ += g ν, P −= g P[j, :]. r [nx]
+        (or a scalar): the measurement noise variances. Returns a dict with xhat, P (new arrays), innovation [B, nx], nis [B] and
+        first_bad [B] (−1, or the first component whose s was not a finite number > 0 and which was skipped)."""
+        measured, _, r = _variances(self.nx, measured, None, r)
+        if r is None:
+            raise ValueError("r must be given")
+        xhat, P = self._estimate_arrays(xhat, P)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != (self.B, self.nx):
+            raise ValueError("y must have shape [B, nx]")
+        out = dict(xhat=xhat, P=P, innovation=np.empty((self.B, self.nx)), nis=np.empty(self.B), first_bad=np.empty(self.B, dtype=np.int32))
+        _ffi.check(_ffi.lib().ilqr_estimate_update(self._h, _i32p(measured), _p(r), _p(y), _p(xhat), _p(P), _p(out["innovation"]), _p(out["nis"]),
+                                                   _i32p(out["first_bad"])))
+        return out
+
+    def estimate_update_device_(self, d_xhat_ptr, d_P_ptr, d_y_ptr, r, measured=None, d_innovation_ptr=None, d_nis_ptr=None, d_first_bad_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not wanted); r and measured stay host arrays;
+        asynchronous on the handle's stream."""
+        measured, _, r = _variances(self.nx, measured, None, r)
+        if r is None:
+            raise ValueError("r must be given")
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_estimate_update_device(self._h, _i32p(measured), _p(r), vp(d_y_ptr), vp(d_xhat_ptr), vp(d_P_ptr),
+                                                          vp(d_innovation_ptr), vp(d_nis_ptr), vp(d_first_bad_ptr)))
+
     def plant_score_(self, x, u, w_plant=None):
         """The score of plant steps on the device (ilqr_plant_score): the realised stage cost and constraint violation of the states a
         plant visited and the actions it applied, x [B, steps + 1, nx] and u [B, steps, nu] as plant_step_ returns them (the last row
@@ -456,7 +538,7 @@ class Solver:
 
     def mpc_run_(self, periods, steps=1, x0=None, plant_feedback=False, shift_feedback=False, shift_tail="hold", warm=True, duals_tail="hold",
                  duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None, w_preview=None, score=False, u_min=None, u_max=None,
-                 sigma_y=None, delay=0):
+                 sigma_y=None, delay=0, estimator=None):
         """The closed MPC loop, enqueued once and synchronised once (ilqr_mpc_run): for each of `periods` re-solves plant_step_(steps)
         on a plant state that stays on the device, shift_horizon_(steps, x1 = the plant state), and shift_duals_ + solve_warm_ (warm)
         or solve_. x0 [B, nx]: the first plant state (None: x̄_0 of the handle); w_plant [B, periods · steps, num_parameter]. Returns an
@@ -468,7 +550,11 @@ class Solver:
         u_min, u_max [nu]: the actuator's limits, as plant_step_'s; sigma_y [nx]: measurement noise, as plant_measure_'s, on the plant
         state the shift is handed; delay=1: the re-solve is anchored at a one-period model prediction from a measurement one period
         old (the solve takes a period), instead of at a measurement of the state it is applied from. Any of them goes through
-        ilqr_mpc_run_io, and the result carries y_cl [B, periods, nx], what the controller was given, and saturated [B]."""
+        ilqr_mpc_run_io, and the result carries y_cl [B, periods, nx], what the controller was given, and saturated [B].
+        estimator = dict(r=, q=None, measured=None, xhat0=None, P0=): an extended Kalman filter between the measurement and the
+        controller (ilqr_mpc_run_est) — estimate_predict_ under the plan in flight and estimate_update_ with the period's measurement, in
+        the order `delay` sets; the re-solve is anchored at the estimate. xhat0 [B, nx] (None: the first plant state), P0 [B, nx, nx].
+        The result carries xhat, pdiag, nis and the last covariance P; y_cl is then the measurement taken."""
         periods = int(periods)
         if periods < 1:
             raise ValueError("periods must be >= 1")
@@ -477,6 +563,21 @@ class Solver:
         u_min, u_max = _limits(self.nu, u_min, u_max)
         sigma_y = _sigma_y(self.nx, sigma_y)
         io = u_min is not None or u_max is not None or sigma_y is not None or delay == 1
+        if estimator is not None:
+            unknown = set(estimator) - {"measured", "q", "r", "xhat0", "P0"}
+            if unknown:
+                raise ValueError("estimator: unknown keys %s" % sorted(unknown))
+            if estimator.get("r") is None or estimator.get("P0") is None:
+                raise ValueError("estimator needs r and P0")
+            e_measured, e_q, e_r = _variances(self.nx, estimator.get("measured"), estimator.get("q"), estimator["r"])
+            e_P = np.array(estimator["P0"], dtype=np.float64, order="C")
+            if e_P.shape != (self.B, self.nx, self.nx):
+                raise ValueError("P0 must have shape [B, nx, nx]")
+            e_xhat0 = estimator.get("xhat0")
+            if e_xhat0 is not None:
+                e_xhat0 = np.ascontiguousarray(e_xhat0, dtype=np.float64)
+                if e_xhat0.shape != (self.B, self.nx):
+                    raise ValueError("xhat0 must have shape [B, nx]")
         steps, sigma_x, w_plant = self._plant_arguments(steps, sigma_x, w_plant, periods * int(steps))
         if w_preview is not None:
             w_preview = np.ascontiguousarray(w_preview, dtype=np.float64)
@@ -498,9 +599,21 @@ class Solver:
         log, nf = np.empty((self.B, periods, _ffi.MPC_LOG_W)), np.empty(self.B, dtype=np.int32)
         cl_cost, cl_violation = (np.empty((self.B, R)), np.empty((self.B, R))) if score else (None, None)
         y_cl = saturated = None
+
+        def nul(a):
+            return _p(a) if a is not None else None
+        if estimator is not None:
+            pio = _ffi.PlantIO(nul(u_min), nul(u_max), nul(sigma_y), int(delay), 0)
+            est = _ffi.Estimator(_i32p(e_measured), nul(e_q), _p(e_r))
+            y_cl, saturated = np.empty((self.B, periods, self.nx)), np.empty(self.B, dtype=np.int32)
+            xhat, pdiag, nis = np.empty((self.B, periods, self.nx)), np.empty((self.B, periods, self.nx)), np.empty((self.B, periods))
+            _ffi.check(_ffi.lib().ilqr_mpc_run_est(self._h, C.byref(d), C.byref(pio), C.byref(est), nul(x0), nul(e_xhat0), _p(e_P), nul(w_plant),
+                                                   nul(w_preview), _p(x), _p(u), _p(log), _i32p(nf), nul(cl_cost), nul(cl_violation), _p(y_cl),
+                                                   _i32p(saturated), _p(xhat), _p(pdiag), _p(nis)))
+            ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
+            return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)},
+                             nf, cl_cost, cl_violation, y_cl, saturated, xhat, pdiag, nis, e_P)
         if io:
-            def nul(a):
-                return _p(a) if a is not None else None
             pio = _ffi.PlantIO(nul(u_min), nul(u_max), nul(sigma_y), int(delay), 0)
             y_cl, saturated = np.empty((self.B, periods, self.nx)), np.empty(self.B, dtype=np.int32)
             _ffi.check(_ffi.lib().ilqr_mpc_run_io(self._h, C.byref(d), C.byref(pio), nul(x0), nul(w_plant), nul(w_preview), _p(x), _p(u), _p(log),

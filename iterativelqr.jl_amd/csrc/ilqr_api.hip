@@ -100,7 +100,7 @@ enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
 enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
 enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_SATURATED, PLANT_XC,
-       PLANT_Y, PLANT_STAGES };
+       PLANT_Y, EST_P, EST_Y, EST_INNOVATION, EST_NIS, EST_FIRST_BAD, EST_XHAT_CL, EST_PDIAG_CL, EST_NIS_CL, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -166,7 +166,9 @@ struct ilqr_handle {
     // ilqr_mpc_run_preview: w_preview and the realised scores of the run too; ilqr_plant_score: its host form (x, u and w_plant in
     // the stages of x_out, u_out and w_plant, the two scores in their own); ilqr_plant_step_limited: the saturation counts too;
     // ilqr_plant_measure: x in the stage of the plant state, y in its own; ilqr_mpc_run_io: the controller's state xc, what it was
-    // given per period (y_cl, in the stage of y) and the saturation counts of the run
+    // given per period (y_cl, in the stage of y) and the saturation counts of the run; ilqr_estimate_predict / _update: the estimate in
+    // the stage of xc, y in its own, the covariance, the innovation, nis and first_bad; ilqr_mpc_run_est: the covariance, the period's
+    // measurement and nis, and the three per-period logs of the filter
     Stage plant[PLANT_STAGES];
 };
 
@@ -385,6 +387,17 @@ __global__ void device_math_kernel(int which, const double* x, double* y, int n)
         default: ilqr::sincos_fast(v, s, r); break;
     }
     y[i] = r;
+}
+
+// ilqr_mpc_run_est: row p of the filter's per-period logs, one thread per (instance, component); plain vector stores
+__global__ void estimate_log_kernel(int B, int n, int periods, int p, const double* xhat, const double* P, const double* nis, double* xhat_cl,
+                                    double* pdiag_cl, double* nis_cl) {
+    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (size_t)B * n) return;
+    const size_t b = e / n, j = e % n, row = b * (size_t)periods + (size_t)p;
+    if (xhat_cl) xhat_cl[row * n + j] = xhat[e];
+    if (pdiag_cl) pdiag_cl[row * n + j] = P[b * n * n + j * (n + 1)];
+    if (nis_cl && j == 0) nis_cl[row] = nis[b];
 }
 
 }  // namespace
@@ -1569,19 +1582,143 @@ int ilqr_plant_score(ilqr_handle* h, int32_t steps, const double* w_plant, const
     return stage_out(h, arrays);
 }
 
+// ---- the extended Kalman filter between sensor and controller (ilqr_device_estimate.hpp)
+// a variance vector (q): finite and >= 0; (r): finite and > 0 where measured; a mask entry: 0 or 1; their first `count` entries
+static int variance_check(const int32_t* measured, const double* q, const double* r, int count, const std::string& me) {
+    for (int j = 0; j < count; ++j) {
+        if (measured && measured[j] != 0 && measured[j] != 1) return fail(ILQR_ERR_INVALID, me + ": a mask entry must be 0 or 1");
+        if (q && (!(q[j] >= 0.0) || !std::isfinite(q[j]))) return fail(ILQR_ERR_INVALID, me + ": q must be finite and >= 0");
+        if (r && (!measured || measured[j]) && (!(r[j] > 0.0) || !std::isfinite(r[j])))
+            return fail(ILQR_ERR_INVALID, me + ": r must be finite and > 0 where measured");
+    }
+    return ILQR_OK;
+}
+
+// everything that can be refused without touching the GPU; what needs no handle comes first (of a vector: its first entry)
+static int predict_check(const ilqr_handle* h, int32_t steps, int32_t feedback, const double* u_min, const double* u_max, const double* q,
+                         const char* who) {
+    const std::string me(who);
+    ILQR_TRY(variance_check(nullptr, q, nullptr, 1, me));
+    ILQR_TRY(plant_check(h, steps, feedback, 0, 0, steps, nullptr, u_min, u_max, nullptr, who));
+    return variance_check(nullptr, q, nullptr, h->L.nx, me);
+}
+static int update_check(const ilqr_handle* h, const int32_t* measured, const double* r, const char* who) {
+    const std::string me(who);
+    if (!r) return fail(ILQR_ERR_INVALID, me + ": null r");
+    ILQR_TRY(variance_check(measured, nullptr, r, 1, me));
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
+    return variance_check(measured, nullptr, r, h->L.nx, me);
+}
+
+// xhat, P: device pointers on h's device
+static int predict_launch(ilqr_handle* h, int32_t steps, int32_t feedback, const double* u_min, const double* u_max, const double* q, double* xhat,
+                          double* P) {
+    if (!h->vt->launch_estimate_predict) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
+    ilqr::EstArgs a = {};
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.feedback = feedback ? 1 : 0; a.xhat = xhat; a.P = P;
+    a.clamp = (u_min || u_max) ? 1 : 0;
+    for (int j = 0; a.clamp && j < h->L.nu; ++j) {
+        a.u_lo[j] = u_min ? u_min[j] : -HUGE_VAL;
+        a.u_hi[j] = u_max ? u_max[j] : HUGE_VAL;
+    }
+    for (int j = 0; q && j < h->L.nx; ++j) a.q[j] = q[j];                      // by value: the caller's array may go away at once
+    if (h->vt->launch_estimate_predict(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "estimator time update launch failed");
+    return ILQR_OK;
+}
+
+// y, xhat, P, innovation, nis, first_bad: device pointers on h's device (the last three: or null)
+static int update_launch(ilqr_handle* h, const int32_t* measured, const double* r, const double* y, double* xhat, double* P, double* innovation,
+                         double* nis, int32_t* first_bad) {
+    if (!h->vt->launch_estimate_update) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
+    ilqr::EstArgs a = {};
+    a.B = h->B; a.xhat = xhat; a.P = P; a.y = y; a.innovation = innovation; a.nis = nis; a.first_bad = first_bad;
+    for (int j = 0; j < h->L.nx; ++j) {
+        if (!measured || measured[j]) a.mask[j / 32] |= 1u << (j % 32);
+        a.r[j] = r[j];
+    }
+    if (h->vt->launch_estimate_update(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "estimator measurement update launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_estimate_predict_device(ilqr_handle* h, int32_t steps, int32_t feedback, const double* u_min, const double* u_max, const double* q,
+                                 double* xhat, double* P) {
+    if (!xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_predict_device: null xhat or P");
+    ILQR_TRY(predict_check(h, steps, feedback, u_min, u_max, q, "ilqr_estimate_predict_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_estimate_predict");
+    HIP_TRY(hipSetDevice(h->device));
+    return predict_launch(h, steps, feedback, u_min, u_max, q, xhat, P);
+}
+
+int ilqr_estimate_predict(ilqr_handle* h, int32_t steps, int32_t feedback, const double* u_min, const double* u_max, const double* q, double* xhat,
+                          double* P) {
+    if (!xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_predict: null xhat or P");
+    ILQR_TRY(predict_check(h, steps, feedback, u_min, u_max, q, "ilqr_estimate_predict"));
+    const size_t n = (size_t)h->L.nx;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_estimate_predict(s, steps, feedback, u_min, u_max, q, xhat + lo * n, P + lo * n * n); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    const Staged s_x = {&h->plant[PLANT_XC], xhat, xhat, B * n * 8};           // the estimate and its covariance go in and come back
+    const Staged s_P = {&h->plant[EST_P], P, P, B * n * n * 8};
+    const auto arrays = {s_x, s_P};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(predict_launch(h, steps, feedback, u_min, u_max, q, s_x.dev<double>(), s_P.dev<double>()));
+    return stage_out(h, arrays);
+}
+
+int ilqr_estimate_update_device(ilqr_handle* h, const int32_t* measured, const double* r, const double* y, double* xhat, double* P,
+                                double* innovation, double* nis, int32_t* first_bad) {
+    if (!xhat || !P || !y) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update_device: null xhat, P or y");
+    ILQR_TRY(update_check(h, measured, r, "ilqr_estimate_update_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_estimate_update");
+    HIP_TRY(hipSetDevice(h->device));
+    return update_launch(h, measured, r, y, xhat, P, innovation, nis, first_bad);
+}
+
+int ilqr_estimate_update(ilqr_handle* h, const int32_t* measured, const double* r, const double* y, double* xhat, double* P, double* innovation,
+                         double* nis, int32_t* first_bad) {
+    if (!xhat || !P || !y) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update: null xhat, P or y");
+    ILQR_TRY(update_check(h, measured, r, "ilqr_estimate_update"));
+    const size_t n = (size_t)h->L.nx;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_estimate_update(s, measured, r, y + lo * n, xhat + lo * n, P + lo * n * n, at(innovation, lo * n), at(nis, lo), at(first_bad, lo)); },
+        true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    const Staged s_y = staged_in(h->plant[EST_Y], y, B * n * 8);
+    const Staged s_x = {&h->plant[PLANT_XC], xhat, xhat, B * n * 8};
+    const Staged s_P = {&h->plant[EST_P], P, P, B * n * n * 8};
+    const Staged s_inn = staged_out(h->plant[EST_INNOVATION], innovation, B * n * 8);
+    const Staged s_nis = staged_out(h->plant[EST_NIS], nis, B * 8);
+    const Staged s_bad = staged_out(h->plant[EST_FIRST_BAD], first_bad, B * 4);
+    const auto arrays = {s_y, s_x, s_P, s_inn, s_nis, s_bad};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(update_launch(h, measured, r, s_y.dev<const double>(), s_x.dev<double>(), s_P.dev<double>(), s_inn.dev<double>(), s_nis.dev<double>(),
+                           s_bad.dev<int32_t>()));
+    return stage_out(h, arrays);
+}
+
 // ---- the closed MPC loop, enqueued once: per period plant step, score, horizon shift, dual shift, solve, log row
 static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
 // everything its constituents refuse for these arguments, before any launch
 // The seam between plant and controller is in use: limits, measurement noise, a delay, or one of the two outputs that report on it.
 // Otherwise the loop hands the shift the plant state itself: no launch, no buffer and no argument of it differs from ilqr_mpc_run's.
-static bool mpc_measured(const ilqr_plant_io* io, const double* y_cl, const int32_t* saturated) {
-    return (io && (io->u_min || io->u_max || io->sigma_y || io->delay)) || y_cl || saturated;
+static bool mpc_measured(const ilqr_plant_io* io, const double* y_cl, const int32_t* saturated, const ilqr_estimator* est = nullptr) {
+    return (io && (io->u_min || io->u_max || io->sigma_y || io->delay)) || y_cl || saturated || est;
 }
 // measured: the run goes through the measurement slot (mpc_measured)
 static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, bool measured, const double* w_plant,
-                     const double* w_preview, const double* cl_cost, const double* cl_violation, const char* who) {
+                     const double* w_preview, const double* cl_cost, const double* cl_violation, const ilqr_estimator* est, const double* xhat0,
+                     const double* Pcov, const double* xhat_cl, const double* pdiag_cl, const double* nis_cl, const char* who) {
     const std::string me(who);
     if (!d) return fail(ILQR_ERR_INVALID, me + ": null descriptor");
+    if (!est && (xhat0 || Pcov || xhat_cl || pdiag_cl || nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
+    if (est && !Pcov) return fail(ILQR_ERR_INVALID, me + ": an estimator with a null P");
+    if (est) {                                     // what needs no handle, as the two estimator calls order it
+        if (!est->r) return fail(ILQR_ERR_INVALID, me + ": null r");
+        ILQR_TRY(variance_check(est->measured, est->q, est->r, 1, me));
+    }
     if (d->periods < 1) return fail(ILQR_ERR_INVALID, me + ": periods must be >= 1");
     if (cl_violation && !cl_cost) return fail(ILQR_ERR_INVALID, me + ": cl_violation without cl_cost: the two scores come from one launch");
     if (io && io->delay != 0 && io->delay != 1) return fail(ILQR_ERR_INVALID, me + ": delay must be 0 or 1");
@@ -1601,27 +1738,32 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_pl
         if (!h->constrained) return fail(ILQR_ERR_INVALID, me + ": warm on a handle created unconstrained: it has no duals to keep");
         ILQR_TRY(duals_check(h, d->steps, d->duals_tail, d->duals_penalty, who));
     }
+    if (est) ILQR_TRY(variance_check(est->measured, est->q, est->r, h->L.nx, me));
     return ILQR_OK;
 }
 
 // ilqr_mpc_run is this with w_preview, cl_cost and cl_violation null and nothing measured (mpc_measured); ilqr_mpc_run_preview with
-// nothing measured: no launch, no buffer and no argument of it changes then
+// nothing measured: no launch, no buffer and no argument of it changes then; ilqr_mpc_run_io with est and what follows it null.
+// est: the filter stands between the measurement and the controller's state xc, which then IS the estimate x̂
 static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const double* x0, const double* w_plant, const double* w_preview,
                    double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
-                   int32_t* saturated, const char* who) {
-    const bool measured = mpc_measured(io, y_cl, saturated);
-    ILQR_TRY(mpc_check(h, d, io, measured, w_plant, w_preview, cl_cost, cl_violation, who));
+                   int32_t* saturated, const char* who, const ilqr_estimator* est = nullptr, const double* xhat0 = nullptr, double* Pcov = nullptr,
+                   double* xhat_cl = nullptr, double* pdiag_cl = nullptr, double* nis_cl = nullptr) {
+    const bool measured = mpc_measured(io, y_cl, saturated, est);
+    ILQR_TRY(mpc_check(h, d, io, measured, w_plant, w_preview, cl_cost, cl_violation, est, xhat0, Pcov, xhat_cl, pdiag_cl, nis_cl, who));
     const size_t P = (size_t)d->periods, k = (size_t)d->steps, R = P * k, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         ilqr_mpc_desc sd = *d;
         sd.first_instance += (int64_t)lo;
         return mpc_run(s, &sd, io, at(x0, lo * n), at(w_plant, lo * R * nwu), at(w_preview, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
                        at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), at(y_cl, lo * P * n),
-                       at(saturated, lo), who); }, true);
+                       at(saturated, lo), who, est, at(xhat0, lo * n), at(Pcov, lo * n * n), at(xhat_cl, lo * P * n), at(pdiag_cl, lo * P * n),
+                       at(nis_cl, lo * P)); }, true);
     if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
     const bool score = cl_cost != nullptr;
     if (score && !h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
     if (measured && !h->vt->launch_plant_measure) return fail(ILQR_ERR_MODEL, "this model module has no measurement kernel");
+    if (est && (!h->vt->launch_estimate_predict || !h->vt->launch_estimate_update)) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
     const Staged s_x = staged_in(h->plant[PLANT_X], x0, B * n * 8);
@@ -1635,7 +1777,13 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
     const Staged s_viol = staged_out(h->plant[PLANT_VIOL], cl_violation, B * R * 8);
     const Staged s_y_cl = staged_out(h->plant[PLANT_Y], y_cl, B * P * n * 8);
     const Staged s_saturated = staged_out(h->plant[PLANT_SATURATED], saturated, B * 4);
-    const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol, s_y_cl, s_saturated};
+    const Staged s_xhat0 = staged_in(h->plant[PLANT_XC], xhat0, B * n * 8);
+    const Staged s_P = {&h->plant[EST_P], Pcov, Pcov, Pcov ? B * n * n * 8 : 0};          // P0 goes in, the last covariance comes back
+    const Staged s_xhat_cl = staged_out(h->plant[EST_XHAT_CL], xhat_cl, B * P * n * 8);
+    const Staged s_pdiag_cl = staged_out(h->plant[EST_PDIAG_CL], pdiag_cl, B * P * n * 8);
+    const Staged s_nis_cl = staged_out(h->plant[EST_NIS_CL], nis_cl, B * P * 8);
+    const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol, s_y_cl, s_saturated, s_xhat0, s_P, s_xhat_cl, s_pdiag_cl,
+                         s_nis_cl};
     // Every buffer of the run exists before its first launch — the plant state also without an x0, what the shift would allocate
     // in its first call, the closed-loop trajectory the score reads even when the caller does not ask for it, and the controller's
     // state of a measured run — so that nothing between the first plant launch and the synchronise at the end waits for the device.
@@ -1647,6 +1795,10 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
         ILQR_TRY(grow(h, h->plant[PLANT_U_OUT], B * R * m * 8));
     }
     if (measured) ILQR_TRY(grow(h, h->plant[PLANT_XC], B * n * 8));
+    if (est) {                                     // the period's measurement and nis
+        ILQR_TRY(grow(h, h->plant[EST_Y], B * n * 8));
+        ILQR_TRY(grow(h, h->plant[EST_NIS], B * 8));
+    }
     ILQR_TRY(stage_in(h, arrays));
     double* xp = (double*)h->plant[PLANT_X].p;
     double* xc = measured ? (double*)h->plant[PLANT_XC].p : xp;        // what the shift is handed: the controller's view of the plant state
@@ -1659,8 +1811,17 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
     if (!x0) HIP_TRY(hipMemcpy2DAsync(xp, n * 8, h->ws + h->L.xb, (size_t)h->L.stride * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
     if (s_nonfinite.bytes) HIP_TRY(hipMemsetAsync(s_nonfinite.st->p, 0xff, B * 4, h->stream));       // -1: the plant kernel keeps the first mark
     if (s_saturated.bytes) HIP_TRY(hipMemsetAsync(s_saturated.st->p, 0, B * 4, h->stream));          // the plant kernel adds to it
+    double* ym = est ? (double*)h->plant[EST_Y].p : xc;                  // where the measurement lands: with a filter xc is the estimate
+    double* d_nis = est ? (double*)h->plant[EST_NIS].p : nullptr;
+    const bool est_log = s_xhat_cl.bytes || s_pdiag_cl.bytes || s_nis_cl.bytes;
+    if (est && !xhat0) HIP_TRY(hipMemcpyAsync(xc, xp, B * n * 8, hipMemcpyDeviceToDevice, h->stream));              // x̂_0 = the first plant state
     for (int32_t p = 0; p < d->periods; ++p) {
-        if (delayed) {
+        if (delayed && est) {
+            // the measurement of the state at p·k corrects the estimate, which then moves on to (p+1)·k under the plan in flight
+            ILQR_TRY(measure_launch(h, d->seed, d->first_instance, p * d->steps, sigma_y, xp, ym));
+            ILQR_TRY(update_launch(h, est->measured, est->r, ym, xc, s_P.dev<double>(), nullptr, d_nis, nullptr));
+            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, est->q, xc, s_P.dev<double>()));
+        } else if (delayed) {
             // the solve of this period started one period ago: from a measurement of the state at p·k, moved on by the controller's
             // own model under the plan in flight — same feedback and limits, no process noise, the handle's parameters, no outputs
             ILQR_TRY(measure_launch(h, d->seed, d->first_instance, p * d->steps, sigma_y, xp, xc));
@@ -1674,9 +1835,19 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
         a.w_ld = (long long)R; a.x_ld = (long long)R + 1; a.u_ld = (long long)R;                     // rows p·k .. of the run's arrays
         a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
         if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
-        if (measured && !delayed) ILQR_TRY(measure_launch(h, d->seed, d->first_instance, (p + 1) * d->steps, sigma_y, xp, xc));
-        if (s_y_cl.bytes)                          // row p of y_cl: what the controller is given
-            HIP_TRY(hipMemcpy2DAsync(s_y_cl.dev<double>() + (size_t)p * n, P * n * 8, xc, n * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));
+        if (measured && !delayed) ILQR_TRY(measure_launch(h, d->seed, d->first_instance, (p + 1) * d->steps, sigma_y, xp, ym));
+        if (est && !delayed) {                     // the estimate moves on to (p+1)·k under the plan in flight, then takes the measurement in
+            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, est->q, xc, s_P.dev<double>()));
+            ILQR_TRY(update_launch(h, est->measured, est->r, ym, xc, s_P.dev<double>(), nullptr, d_nis, nullptr));
+        }
+        if (s_y_cl.bytes)                          // row p of y_cl: what the controller is given, with a filter the measurement taken
+            HIP_TRY(hipMemcpy2DAsync(s_y_cl.dev<double>() + (size_t)p * n, P * n * 8, ym, n * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));
+        if (est_log) {
+            const unsigned grid = (unsigned)((B * n + 255) / 256);
+            hipLaunchKernelGGL(estimate_log_kernel, dim3(grid), dim3(256), 0, h->stream, (int)B, (int)n, d->periods, p, xc, s_P.dev<double>(), d_nis,
+                               s_xhat_cl.dev<double>(), s_pdiag_cl.dev<double>(), s_nis_cl.dev<double>());
+            if (hipGetLastError() != hipSuccess) return fail(ILQR_ERR_HIP, "estimator log launch failed");
+        }
         if (score) {                               // before the shift: it overwrites the θ rows 0 .. k−1 the plant ran under
             ilqr::ScoreArgs q = score_args(h, d->steps);
             q.w = a.w; q.x = d_x_cl; q.u = d_u_cl; q.cost = s_cost.dev<double>(); q.viol = s_viol.dev<double>();
@@ -1710,6 +1881,13 @@ int ilqr_mpc_run_io(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io*
                     double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
                     int32_t* saturated) {
     return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_io");
+}
+
+int ilqr_mpc_run_est(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const ilqr_estimator* est, const double* x0, const double* xhat0,
+                     double* P, const double* w_plant, const double* w_preview, double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite,
+                     double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl, double* pdiag_cl, double* nis_cl) {
+    return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_est", est,
+                   xhat0, P, xhat_cl, pdiag_cl, nis_cl);
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

@@ -2331,10 +2331,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_duals.hpp"
 #include "ilqr_device_plant.hpp"
 #include "ilqr_device_score.hpp"
+#include "ilqr_device_estimate.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 19   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 20   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2374,6 +2375,10 @@ extern "C" struct ilqr_model_vtable {
     int (*launch_plant_score)(const ilqr::ScoreArgs* a, void* stream);
     // what the controller is given of a plant state: a copy, or the state plus measurement noise (ilqr_device_plant.hpp)
     int (*launch_plant_measure)(const ilqr::MeasureArgs* a, void* stream);
+    // the extended Kalman filter between sensor and controller: time update under the head of the plan, measurement update; both
+    // read the workspace only (ilqr_device_estimate.hpp)
+    int (*launch_estimate_predict)(const ilqr::EstArgs* a, void* stream);
+    int (*launch_estimate_update)(const ilqr::EstArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2435,7 +2440,8 @@ struct ModelModule {
                                              jac_nvar(), hess_nnz(), is_large<M>::value ? &launch_mirror : nullptr,
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
                                              &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>, &launch_shift_duals<M>,
-                                             &launch_plant<M>, &launch_mpc_log<M>, &launch_plant_score<M>, &launch_plant_measure<M>};
+                                             &launch_plant<M>, &launch_mpc_log<M>, &launch_plant_score<M>, &launch_plant_measure<M>,
+                                             &launch_estimate_predict<M>, &launch_estimate_update<M>};
         return &vt;
     }
 };

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO, estimate_predict!, estimate_update!, mpc_run_est!, Estimator,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 import Libdl
@@ -441,6 +441,94 @@ function mpc_run_io!(s::Solver; periods::Integer, steps::Integer = 1, plant_feed
                     x, u, log, nf, score ? cl_cost : nul, score ? cl_violation : nul, y_cl, saturated))
     end
     return x, u, log, nf, cl_cost, cl_violation, y_cl, saturated
+end
+
+# The time update of the extended Kalman filter on the device (ilqr_estimate_predict): the estimates xhat :: (nx, B) move on by
+# `steps` control periods under the head of the handle's plan as plant_step_limited! moves a state without noise, and per step
+# P ← F P Fᵀ + diag(q), F the model's dynamics state Jacobian at the estimate before it moves. P :: (nx, nx, B), symmetric. Both
+# arrays are updated in place.
+function estimate_predict!(s::Solver, xhat::Matrix{Float64}, P::Array{Float64,3}; steps::Integer = 1, feedback::Bool = false,
+                           u_min::Union{Nothing,Vector{Float64}} = nothing, u_max::Union{Nothing,Vector{Float64}} = nothing,
+                           q::Union{Nothing,Vector{Float64}} = nothing)
+    @assert size(xhat) == (s.nx, s.B) && size(P) == (s.nx, s.nx, s.B) && 1 <= steps <= s.T - 1
+    @assert (u_min === nothing || length(u_min) == s.nu) && (u_max === nothing || length(u_max) == s.nu) && (q === nothing || length(q) == s.nx)
+    nul = Ptr{Float64}(C_NULL)
+    check(ccall((:ilqr_estimate_predict, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, Int32(steps), Int32(feedback ? 1 : 0), u_min === nothing ? nul : u_min, u_max === nothing ? nul : u_max,
+                q === nothing ? nul : q, xhat, P))
+    return xhat, P
+end
+
+# The measurement update (ilqr_estimate_update): the components j of y :: (nx, B) with measured[j] == 1 (nothing: all) are taken in
+# one after the other with the variances r. xhat and P are updated in place. Returns (innovation :: (nx, B), nis :: B, first_bad :: B).
+function estimate_update!(s::Solver, xhat::Matrix{Float64}, P::Array{Float64,3}, y::Matrix{Float64}, r::Vector{Float64};
+                          measured::Union{Nothing,Vector{Int32}} = nothing)
+    @assert size(xhat) == (s.nx, s.B) && size(P) == (s.nx, s.nx, s.B) && size(y) == (s.nx, s.B) && length(r) == s.nx
+    @assert measured === nothing || length(measured) == s.nx
+    innovation = Matrix{Float64}(undef, s.nx, s.B)
+    nis = Vector{Float64}(undef, s.B)
+    first_bad = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_estimate_update, LIB[]), Cint,
+                (Ptr{Cvoid}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                s.handle, measured === nothing ? Ptr{Int32}(C_NULL) : measured, r, y, xhat, P, innovation, nis, first_bad))
+    return innovation, nis, first_bad
+end
+
+# ilqr_estimator, field for field
+struct Estimator
+    measured::Ptr{Int32}
+    q::Ptr{Float64}
+    r::Ptr{Float64}
+end
+
+# mpc_run_io! with the filter between sensor and controller (ilqr_mpc_run_est): the re-solve is anchored at the estimate. P0 ::
+# (nx, nx, B) holds the last covariance on return. Returns (x, u, log, first_nonfinite, y_cl, saturated, xhat :: (nx, periods, B),
+# pdiag :: (nx, periods, B), nis :: (periods, B), P0). (The symbol is looked up by hand, as mpc_run_io!'s.)
+function mpc_run_est!(s::Solver, r::Vector{Float64}, P0::Array{Float64,3}; periods::Integer, steps::Integer = 1, plant_feedback::Bool = false,
+                      shift_feedback::Bool = false, shift_tail::Symbol = :hold, warm::Bool = true, duals_tail::Symbol = :hold,
+                      duals_penalty::Symbol = :keep, seed::Integer = 0, first_instance::Integer = 0,
+                      sigma_x::Union{Nothing,Vector{Float64}} = nothing, x0::Union{Nothing,Matrix{Float64}} = nothing,
+                      xhat0::Union{Nothing,Matrix{Float64}} = nothing, u_min::Union{Nothing,Vector{Float64}} = nothing,
+                      u_max::Union{Nothing,Vector{Float64}} = nothing, sigma_y::Union{Nothing,Vector{Float64}} = nothing, delay::Integer = 0,
+                      measured::Union{Nothing,Vector{Int32}} = nothing, q::Union{Nothing,Vector{Float64}} = nothing)
+    @assert periods >= 1 && 1 <= steps <= s.T - 1 && (delay == 0 || delay == 1)
+    @assert length(r) == s.nx && size(P0) == (s.nx, s.nx, s.B) && (q === nothing || length(q) == s.nx) && (measured === nothing || length(measured) == s.nx)
+    @assert (x0 === nothing || size(x0) == (s.nx, s.B)) && (xhat0 === nothing || size(xhat0) == (s.nx, s.B))
+    R = periods * steps
+    nul = Ptr{Float64}(C_NULL)
+    x = Array{Float64,3}(undef, s.nx, R + 1, s.B)
+    u = Array{Float64,3}(undef, s.nu, R, s.B)
+    log = Array{Float64,3}(undef, 9, periods, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    y_cl = Array{Float64,3}(undef, s.nx, periods, s.B)
+    saturated = Vector{Int32}(undef, s.B)
+    xhat = Array{Float64,3}(undef, s.nx, periods, s.B)
+    pdiag = Array{Float64,3}(undef, s.nx, periods, s.B)
+    nis = Matrix{Float64}(undef, periods, s.B)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    sig = sigma_x === nothing ? Float64[] : sigma_x
+    lo = u_min === nothing ? Float64[] : u_min
+    hi = u_max === nothing ? Float64[] : u_max
+    sy = sigma_y === nothing ? Float64[] : sigma_y
+    mk = measured === nothing ? Int32[] : measured
+    qq = q === nothing ? Float64[] : q
+    GC.@preserve sig lo hi sy mk qq r begin
+        d = MpcDesc(Int32(periods), Int32(steps), Int32(plant_feedback ? 1 : 0), Int32(shift_feedback ? 1 : 0),
+                    Int32(shift_tail === :hold ? 0 : 1), Int32(warm ? 1 : 0), Int32(duals_tail === :hold ? 0 : 1),
+                    Int32(duals_penalty === :keep ? 0 : 1), UInt64(seed), Int64(first_instance),
+                    sigma_x === nothing ? nul : pointer(sig))
+        io = PlantIO(u_min === nothing ? nul : pointer(lo), u_max === nothing ? nul : pointer(hi),
+                     sigma_y === nothing ? nul : pointer(sy), Int32(delay), Int32(0))
+        est = Estimator(measured === nothing ? Ptr{Int32}(C_NULL) : pointer(mk), q === nothing ? nul : pointer(qq), pointer(r))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_mpc_run_est)
+        check(ccall(fn, Cint, (Ptr{Cvoid}, Ref{MpcDesc}, Ref{PlantIO}, Ref{Estimator}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, d, io, est, x0 === nothing ? nul : x0, xhat0 === nothing ? nul : xhat0, P0, nul, nul, x, u, log, nf, nul, nul, y_cl,
+                    saturated, xhat, pdiag, nis))
+    end
+    return x, u, log, nf, y_cl, saturated, xhat, pdiag, nis, P0
 end
 
 # Solver(...; parameters = θ) — src/solver.jl:12,29; θ :: (nw, T, B)
