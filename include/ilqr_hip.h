@@ -518,6 +518,83 @@ int ilqr_mpc_run_est(ilqr_handle* h, const ilqr_mpc_desc* d,
                      double* pdiag_cl,          /* NULL, or [B][P][nx] */
                      double* nis_cl);           /* NULL, or [B][P] */
 
+/* A linear sensor for the filter and the loop: y = H x + v, v ~ N(0, diag(r)), with ny outputs, 1 <= ny <= 64; ny may be smaller or
+ * LARGER than nx (an absolute link angle q1 + q2, two redundant sensors of one state, a combination of modes). Per instance b:
+ * x̂ [nx]; P [nx][nx], row-major, symmetric, both triangles stored; H [ny][nx], row-major, shared by the batch (per_instance_H == 0) or
+ * one per instance, [B][ny][nx] (per_instance_H == 1); r [ny]; y [ny]; optionally ŷ [ny].
+ *
+ * ilqr_estimate_update_linear, the measurement update. On entry c_j = 0, or with yhat given c_j = ŷ_j − h_j·x̂₀, where x̂₀ is the
+ * estimate on entry and h_j row j of H: ŷ is then the caller's h(x̂₀) of a nonlinear sensor and H its ∂h/∂x there, linearised once at
+ * the prior as an extended Kalman filter does. For j = 0 .. ny−1 in increasing order, on the x̂ and P the previous j left:
+ *     d   = P h_jᵀ, nx sums over the ascending column index
+ *     s_j = h_j·d + r_j;  ν_j = (y_j − c_j) − h_j·x̂. If s_j is not a finite number > 0 the row is skipped and first_bad[b] becomes j
+ *           (the first such j is kept; −1 if there is none)
+ *     g = d / s_j;  x̂ ← x̂ + g · ν_j;  P_ab ← P_ab − g_a · d_b for a >= b, from d as it was, then mirrored: the stored matrix is
+ *           exactly symmetric
+ *     nis[b] = Σ_j ν_j² / s_j over the rows that were updated; innovation[b][j] = ν_j, or 0 where the row was skipped
+ * R being diagonal, the sequence equals the batch update with S = H P Hᵀ + R. The order inside every sum is the kernel's and depends
+ * on the model's sizes and ny alone: the same instance gives the same bits in any batch. The call reads nothing of the handle but
+ * its dimensions, device and stream.
+ *
+ * ilqr_plant_measure_linear, the measurement: y[b][j] = Σ_k H_jk x[b][k], one FMA chain over ascending k starting from +0, then
+ * + sigma_y[j] · z(seed, first_instance + b, 5 + j / 16, step, j % 16) where sigma_y[j] != 0, product and sum rounded separately; z is
+ * ilqr_plant_measure's, unchanged. The key fields are 5 .. 8 — the SAME fields and the same host
+ * twin as ilqr_plant_measure's, ilqr_candidate_noise(seed, first_instance, B, 9, step + 1, 16, z): a run uses one kind of measurement
+ * or the other, never both, so sharing the stream is intended. With H the identity the result is ilqr_plant_measure's.
+ *
+ * Refused (ILQR_ERR_INVALID) before any launch: ny < 1 or ny > 64; a null handle, H, r, y, x, xhat or P; per_instance_H other than
+ * 0 or 1; a non-finite entry of an H given on the host; an r entry that is not finite and > 0; a negative or non-finite sigma_y entry;
+ * nx > 64; for the measurement everything ilqr_plant_measure refuses. Host forms: every array a host array; work on a sharded handle;
+ * synchronous. Device forms: H, y, yhat, xhat, P, innovation, nis, first_bad (update) and H, x, y (measurement) device pointers; r
+ * and sigma_y stay host arrays of ny <= 64 doubles, which travel in the argument segment of a one-wave launch that writes them to
+ * the handle's buffer: they are read when the call is made, so the caller's array may go away at once, successive calls may carry
+ * different values, and nothing waits for the stream. Asynchronous on the handle's stream; refused on a sharded handle. */
+int ilqr_estimate_update_linear(ilqr_handle* h, int32_t ny, int32_t per_instance_H,
+                                const double* H,           /* [ny][nx], or [B][ny][nx] */
+                                const double* r,           /* HOST [ny], finite, > 0 */
+                                const double* y,           /* [B][ny] */
+                                const double* yhat,        /* NULL, or [B][ny] */
+                                double* xhat,              /* [B][nx] in / out */
+                                double* P,                 /* [B][nx][nx] in / out */
+                                double* innovation,        /* NULL, or [B][ny] */
+                                double* nis,               /* NULL, or [B] */
+                                int32_t* first_bad);       /* NULL, or [B] */
+int ilqr_estimate_update_linear_device(ilqr_handle* h, int32_t ny, int32_t per_instance_H, const double* d_H, const double* r, const double* d_y,
+                                       const double* d_yhat, double* d_xhat, double* d_P, double* d_innovation, double* d_nis,
+                                       int32_t* d_first_bad);
+int ilqr_plant_measure_linear(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, int32_t ny,
+                              const double* H,             /* HOST [ny][nx] */
+                              const double* sigma_y,       /* HOST, NULL or [ny], finite, >= 0 */
+                              const double* x,             /* [B][nx] */
+                              double* y);                  /* [B][ny] */
+int ilqr_plant_measure_linear_device(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, int32_t ny, const double* d_H,
+                                     const double* sigma_y, const double* d_x, double* d_y);
+
+/* ilqr_mpc_run_est's loop with the linear sensor in the place of the selection of state components: the measurement becomes
+ * ilqr_plant_measure_linear_device(ny, the shared H, sensor->sigma_y), taken at the same step index, and the update
+ * ilqr_estimate_update_linear_device(ny, shared H, r, no yhat). The time update (with sensor->q), the order of the four calls per
+ * delay, xc = x̂ and the logs xhat_cl, pdiag_cl, nis_cl are ilqr_mpc_run_est's. y_cl[b][p] is the measurement taken, ny numbers. H, r
+ * and sigma_y are copied to the device once, before the first launch; still one enqueue and one synchronise, every buffer grown
+ * before the first launch. With sensor NULL the call is ilqr_mpc_run_io: no launch, buffer or argument differs. Refused
+ * (ILQR_ERR_INVALID) before any launch: everything ilqr_mpc_run_io, ilqr_estimate_predict and the two calls above refuse;
+ * io->sigma_y non-null together with a sensor (the sensor's own [ny] array replaces it); a sensor with P NULL; xhat0, P, xhat_cl,
+ * pdiag_cl or nis_cl without a sensor. Works on a sharded handle. Not offered: a non-diagonal R, a nonlinear h(x, w) generated into
+ * the model, an H that varies with time inside the loop, outlier gating. */
+typedef struct {
+    int32_t ny, reserved;
+    const double* H;           /* HOST [ny][nx], shared by the batch */
+    const double* r;           /* HOST [ny] */
+    const double* q;           /* HOST, NULL or [nx] */
+    const double* sigma_y;     /* HOST, NULL or [ny] */
+} ilqr_sensor;
+int ilqr_mpc_run_sensor(ilqr_handle* h, const ilqr_mpc_desc* d,
+                        const ilqr_plant_io* io,   /* NULL: none */
+                        const ilqr_sensor* sensor, /* NULL: ilqr_mpc_run_io */
+                        const double* x0, const double* xhat0, double* P, const double* w_plant, const double* w_preview, double* x_cl,
+                        double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation,       /* as ilqr_mpc_run_est's */
+                        double* y_cl,              /* NULL, or [B][P][ny] */
+                        int32_t* saturated, double* xhat_cl, double* pdiag_cl, double* nis_cl);
+
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):
  * the reference functions they run are listed per id. */
 enum {

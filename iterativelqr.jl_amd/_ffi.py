@@ -70,6 +70,15 @@ class ilqr_estimator(C.Structure):
 
 
 Estimator = ilqr_estimator
+
+
+class ilqr_sensor(C.Structure):
+    """ilqr_sensor: the linear sensor of ilqr_mpc_run_sensor — ny, H [ny][nx] shared by the batch, the diagonal of R [ny], the diagonal of
+    Q [nx] and the measurement noise [ny] (named as in the header: the static check compares pointer targets by name)."""
+    _fields_ = [("ny", C.c_int32), ("reserved", C.c_int32), ("H", c_double_p), ("r", c_double_p), ("q", c_double_p), ("sigma_y", c_double_p)]
+
+
+Sensor = ilqr_sensor
 MPC_LOG_W = 9
 MPC_LOG_COLUMNS = ("objective", "gradient_norm", "max_violation", "step_size", "iterations", "outer_iterations", "status", "potrf_info",
                    "rollouts")
@@ -186,6 +195,15 @@ SYMBOLS = {
     "ilqr_mpc_run_est": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), C.POINTER(Estimator), c_double_p, c_double_p, c_double_p,
                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
                                    c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
+    "ilqr_estimate_update_linear": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
+                                              c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32)]),
+    "ilqr_estimate_update_linear_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, c_double_p] + [C.c_void_p] * 7),
+    "ilqr_plant_measure_linear": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "ilqr_plant_measure_linear_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, c_double_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "ilqr_mpc_run_sensor": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), C.POINTER(Sensor), c_double_p, c_double_p, c_double_p,
+                                      c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
+                                      c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
     "ilqr_solve":(C.c_int, [C.c_void_p]),
     "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),

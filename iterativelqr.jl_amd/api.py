@@ -451,6 +451,76 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_plant_measure_device(self._h, int(seed), int(first_instance), int(step),
                                                         _p(sigma_y) if sigma_y is not None else None, C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr)))
 
+    def _sensor(self, H, r=None, sigma_y=None, per_instance=True):
+        """the linear sensor's arrays: H [ny, nx] (or, where allowed, [B, ny, nx]: one per instance), r and sigma_y [ny] (or scalars)"""
+        H = np.ascontiguousarray(H, dtype=np.float64)
+        if H.ndim == 3 and not per_instance:
+            raise ValueError("H must have shape [ny, nx] here: one sensor for the batch")
+        if H.ndim not in (2, 3) or H.shape[-1] != self.nx or (H.ndim == 3 and H.shape[0] != self.B):
+            raise ValueError("H must have shape [ny, nx] or [B, ny, nx]")
+        ny = H.shape[-2]
+        vec = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (ny,)))
+        return H, ny, vec(r), vec(sigma_y)
+
+    def estimate_update_linear_(self, xhat, P, y, H, r, yhat=None):
+        """The measurement update of the filter with a linear sensor y = H x + v, v ~ N(0, diag(r)) (ilqr_estimate_update_linear):
+        H [ny, nx] shared by the batch or [B, ny, nx] one per instance, ny smaller or larger than nx (<= 64); the rows are taken in one
+        after the other, d = P h_jᵀ, s = h_j·d + r[j], ν = y_j − h_j·x̂, x̂ += d ν / s, P −= d dᵀ / s. yhat [B, ny]: the caller's h(x̂) of a
+        nonlinear sensor whose Jacobian at x̂ is H — ν is then y_j − ŷ_j − h_j·(x̂ − x̂₀). Returns the dict of estimate_update_:
+        xhat, P (new arrays), innovation [B, ny], nis [B], first_bad [B]."""
+        H, ny, r, _ = self._sensor(H, r)
+        if r is None:
+            raise ValueError("r must be given")
+        xhat, P = self._estimate_arrays(xhat, P)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != (self.B, ny):
+            raise ValueError("y must have shape [B, ny]")
+        if yhat is not None:
+            yhat = np.ascontiguousarray(yhat, dtype=np.float64)
+            if yhat.shape != (self.B, ny):
+                raise ValueError("yhat must have shape [B, ny]")
+        out = dict(xhat=xhat, P=P, innovation=np.empty((self.B, ny)), nis=np.empty(self.B), first_bad=np.empty(self.B, dtype=np.int32))
+        _ffi.check(_ffi.lib().ilqr_estimate_update_linear(self._h, ny, 1 if H.ndim == 3 else 0, _p(H), _p(r), _p(y),
+                                                          _p(yhat) if yhat is not None else None, _p(xhat), _p(P), _p(out["innovation"]),
+                                                          _p(out["nis"]), _i32p(out["first_bad"])))
+        return out
+
+    def estimate_update_linear_device_(self, d_xhat_ptr, d_P_ptr, d_y_ptr, d_H_ptr, ny, r, per_instance_H=False, d_yhat_ptr=None,
+                                       d_innovation_ptr=None, d_nis_ptr=None, d_first_bad_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not wanted), H among them; r stays a host array;
+        asynchronous on the handle's stream."""
+        ny = int(ny)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64), (max(ny, 0),)))
+        def vp(p):
+            return C.c_void_p(p) if p else None
+        _ffi.check(_ffi.lib().ilqr_estimate_update_linear_device(self._h, ny, 1 if per_instance_H else 0, vp(d_H_ptr), _p(r), vp(d_y_ptr),
+                                                                 vp(d_yhat_ptr), vp(d_xhat_ptr), vp(d_P_ptr), vp(d_innovation_ptr), vp(d_nis_ptr),
+                                                                 vp(d_first_bad_ptr)))
+
+    def plant_measure_linear_(self, x, H, step=0, sigma_y=None, seed=0, first_instance=0):
+        """What a linear sensor reads of the plant states x [B, nx] (ilqr_plant_measure_linear): y = H x with H [ny, nx], plus
+        sigma_y[j] · z where sigma_y[j] != 0, z = candidate_noise(seed, first_instance + b, 5 + j // 16, step, j % 16) — plant_measure_'s
+        stream. Returns y [B, ny]."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.B, self.nx):
+            raise ValueError("x must have shape [B, nx]")
+        H, ny, _, sigma_y = self._sensor(H, None, sigma_y, per_instance=False)
+        y = np.empty((self.B, ny))
+        _ffi.check(_ffi.lib().ilqr_plant_measure_linear(self._h, int(seed), int(first_instance), int(step), ny, _p(H),
+                                                        _p(sigma_y) if sigma_y is not None else None, _p(x), _p(y)))
+        return y
+
+    def plant_measure_linear_device_(self, d_x_ptr, d_y_ptr, d_H_ptr, ny, step=0, sigma_y=None, seed=0, first_instance=0):
+        """The same with raw device pointers on the handle's device for x, y and H [ny, nx]; sigma_y stays a host array;
+        asynchronous on the handle's stream."""
+        ny = int(ny)
+        if sigma_y is not None:
+            sigma_y = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_y, dtype=np.float64), (max(ny, 0),)))
+        _ffi.check(_ffi.lib().ilqr_plant_measure_linear_device(self._h, int(seed), int(first_instance), int(step), ny,
+                                                               C.c_void_p(d_H_ptr) if d_H_ptr else None,
+                                                               _p(sigma_y) if sigma_y is not None else None, C.c_void_p(d_x_ptr),
+                                                               C.c_void_p(d_y_ptr)))
+
     def _estimate_arrays(self, xhat, P):
         xhat, P = np.array(xhat, dtype=np.float64, order="C"), np.array(P, dtype=np.float64, order="C")
         if xhat.shape != (self.B, self.nx):
@@ -554,7 +624,10 @@ class Solver:
         estimator = dict(r=, q=None, measured=None, xhat0=None, P0=): an extended Kalman filter between the measurement and the
         controller (ilqr_mpc_run_est) — estimate_predict_ under the plan in flight and estimate_update_ with the period's measurement, in
         the order `delay` sets; the re-solve is anchored at the estimate. xhat0 [B, nx] (None: the first plant state), P0 [B, nx, nx].
-        The result carries xhat, pdiag, nis and the last covariance P; y_cl is then the measurement taken."""
+        The result carries xhat, pdiag, nis and the last covariance P; y_cl is then the measurement taken.
+        estimator = dict(H=, r=, q=None, xhat0=None, P0=, sigma_y=None): the same loop with the linear sensor y = H x + v of
+        plant_measure_linear_ / estimate_update_linear_ (ilqr_mpc_run_sensor), selected by the key H [ny, nx]; r and sigma_y have ny
+        entries, y_cl is [B, periods, ny]. Not together with `measured` or with the loop's own sigma_y."""
         periods = int(periods)
         if periods < 1:
             raise ValueError("periods must be >= 1")
@@ -563,13 +636,22 @@ class Solver:
         u_min, u_max = _limits(self.nu, u_min, u_max)
         sigma_y = _sigma_y(self.nx, sigma_y)
         io = u_min is not None or u_max is not None or sigma_y is not None or delay == 1
+        linear = estimator is not None and "H" in estimator
         if estimator is not None:
-            unknown = set(estimator) - {"measured", "q", "r", "xhat0", "P0"}
+            unknown = set(estimator) - ({"H", "q", "r", "xhat0", "P0", "sigma_y", "measured"} if linear else {"measured", "q", "r", "xhat0", "P0"})
             if unknown:
                 raise ValueError("estimator: unknown keys %s" % sorted(unknown))
+            if linear and "measured" in estimator:
+                raise ValueError("estimator: H and measured exclude each other")
+            if linear and sigma_y is not None:
+                raise ValueError("estimator: with H the sensor's own sigma_y [ny] replaces the loop's")
             if estimator.get("r") is None or estimator.get("P0") is None:
                 raise ValueError("estimator needs r and P0")
-            e_measured, e_q, e_r = _variances(self.nx, estimator.get("measured"), estimator.get("q"), estimator["r"])
+            if linear:
+                e_H, e_ny, e_r, e_sigma = self._sensor(estimator["H"], estimator["r"], estimator.get("sigma_y"), per_instance=False)
+                _, e_q, _ = _variances(self.nx, None, estimator.get("q"), None)
+            else:
+                e_measured, e_q, e_r = _variances(self.nx, estimator.get("measured"), estimator.get("q"), estimator["r"])
             e_P = np.array(estimator["P0"], dtype=np.float64, order="C")
             if e_P.shape != (self.B, self.nx, self.nx):
                 raise ValueError("P0 must have shape [B, nx, nx]")
@@ -604,12 +686,17 @@ class Solver:
             return _p(a) if a is not None else None
         if estimator is not None:
             pio = _ffi.PlantIO(nul(u_min), nul(u_max), nul(sigma_y), int(delay), 0)
-            est = _ffi.Estimator(_i32p(e_measured), nul(e_q), _p(e_r))
-            y_cl, saturated = np.empty((self.B, periods, self.nx)), np.empty(self.B, dtype=np.int32)
+            y_cl, saturated = np.empty((self.B, periods, e_ny if linear else self.nx)), np.empty(self.B, dtype=np.int32)
             xhat, pdiag, nis = np.empty((self.B, periods, self.nx)), np.empty((self.B, periods, self.nx)), np.empty((self.B, periods))
-            _ffi.check(_ffi.lib().ilqr_mpc_run_est(self._h, C.byref(d), C.byref(pio), C.byref(est), nul(x0), nul(e_xhat0), _p(e_P), nul(w_plant),
-                                                   nul(w_preview), _p(x), _p(u), _p(log), _i32p(nf), nul(cl_cost), nul(cl_violation), _p(y_cl),
-                                                   _i32p(saturated), _p(xhat), _p(pdiag), _p(nis)))
+            if linear:
+                est = _ffi.Sensor(e_ny, 0, _p(e_H), _p(e_r), nul(e_q), nul(e_sigma))
+                run = _ffi.lib().ilqr_mpc_run_sensor
+            else:
+                est = _ffi.Estimator(_i32p(e_measured), nul(e_q), _p(e_r))
+                run = _ffi.lib().ilqr_mpc_run_est
+            _ffi.check(run(self._h, C.byref(d), C.byref(pio), C.byref(est), nul(x0), nul(e_xhat0), _p(e_P), nul(w_plant),
+                           nul(w_preview), _p(x), _p(u), _p(log), _i32p(nf), nul(cl_cost), nul(cl_violation), _p(y_cl),
+                           _i32p(saturated), _p(xhat), _p(pdiag), _p(nis)))
             ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
             return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)},
                              nf, cl_cost, cl_violation, y_cl, saturated, xhat, pdiag, nis, e_P)

@@ -100,7 +100,7 @@ enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
 enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
 enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_SATURATED, PLANT_XC,
-       PLANT_Y, EST_P, EST_Y, EST_INNOVATION, EST_NIS, EST_FIRST_BAD, EST_XHAT_CL, EST_PDIAG_CL, EST_NIS_CL, PLANT_STAGES };
+       PLANT_Y, EST_P, EST_Y, EST_INNOVATION, EST_NIS, EST_FIRST_BAD, EST_XHAT_CL, EST_PDIAG_CL, EST_NIS_CL, SENS_H, SENS_R, SENS_SIGMA, SENS_YHAT, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -168,7 +168,8 @@ struct ilqr_handle {
     // ilqr_plant_measure: x in the stage of the plant state, y in its own; ilqr_mpc_run_io: the controller's state xc, what it was
     // given per period (y_cl, in the stage of y) and the saturation counts of the run; ilqr_estimate_predict / _update: the estimate in
     // the stage of xc, y in its own, the covariance, the innovation, nis and first_bad; ilqr_mpc_run_est: the covariance, the period's
-    // measurement and nis, and the three per-period logs of the filter
+    // measurement and nis, and the three per-period logs of the filter; ilqr_estimate_update_linear / ilqr_plant_measure_linear /
+    // ilqr_mpc_run_sensor: H, r, sigma_y and ŷ
     Stage plant[PLANT_STAGES];
 };
 
@@ -398,6 +399,18 @@ __global__ void estimate_log_kernel(int B, int n, int periods, int p, const doub
     if (xhat_cl) xhat_cl[row * n + j] = xhat[e];
     if (pdiag_cl) pdiag_cl[row * n + j] = P[b * n * n + j * (n + 1)];
     if (nis_cl && j == 0) nis_cl[row] = nis[b];
+}
+
+// The device forms of the linear sensor: a host vector of up to 64 doubles (r, sigma_y) goes to the device IN THE ARGUMENT SEGMENT of
+// this launch, so it is read when the call is made — the caller's array may go away at once, successive calls may carry different
+// values, and nothing waits for the stream. Lane j picks entry j through a chain of selects (no indexed read of the segment).
+struct SensorVector { double v[ilqr::SENSOR_MAX_NY]; };
+__global__ void sensor_vector_kernel(SensorVector a, int count, double* out) {
+    const int j = threadIdx.x;
+    double v = 0.0;
+#pragma unroll
+    for (int c = 0; c < ilqr::SENSOR_MAX_NY; ++c) v = (j == c) ? a.v[c] : v;
+    if (j < count) out[j] = v;
 }
 
 }  // namespace
@@ -1699,21 +1712,155 @@ int ilqr_estimate_update(ilqr_handle* h, const int32_t* measured, const double* 
     return stage_out(h, arrays);
 }
 
+// ---- a linear sensor y = H x + v with ny outputs (ilqr_device_sensor.hpp)
+// everything that can be refused without touching the GPU; what needs no handle comes first. H_host: null where H is a device array;
+// r: null where the call takes none (the measurement)
+static int sensor_check(const ilqr_handle* h, int32_t ny, int32_t per_instance_H, const double* H_host, const double* r, const double* sigma_y,
+                        const char* who) {
+    const std::string me(who);
+    if (ny < 1 || ny > ilqr::SENSOR_MAX_NY) return fail(ILQR_ERR_INVALID, me + ": ny must lie in 1 .. 64");
+    if (per_instance_H != 0 && per_instance_H != 1) return fail(ILQR_ERR_INVALID, me + ": per_instance_H must be 0 or 1");
+    for (int j = 0; r && j < ny; ++j)
+        if (!(r[j] > 0.0) || !std::isfinite(r[j])) return fail(ILQR_ERR_INVALID, me + ": r must be finite and > 0");
+    ILQR_TRY(sigma_check(sigma_y, ny, me, "sigma_y"));
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
+    const size_t count = (per_instance_H ? (size_t)h->B : 1) * (size_t)ny * (size_t)h->L.nx;
+    for (size_t e = 0; H_host && e < count; ++e)
+        if (!std::isfinite(H_host[e])) return fail(ILQR_ERR_INVALID, me + ": a non-finite entry of H");
+    return ILQR_OK;
+}
+
+// a host vector of ny doubles (r, sigma_y) of a device form, on its way into its stage without a copy the stream could read late
+static int sensor_vector_upload(ilqr_handle* h, ilqr_handle::Stage& st, const double* v, int32_t ny) {
+    ILQR_TRY(grow(h, st, (size_t)ilqr::SENSOR_MAX_NY * 8));
+    SensorVector a = {};
+    for (int j = 0; j < ny; ++j) a.v[j] = v[j];
+    hipLaunchKernelGGL(sensor_vector_kernel, dim3(1), dim3(ilqr::SENSOR_MAX_NY), 0, h->stream, a, (int)ny, (double*)st.p);
+    if (hipGetLastError() != hipSuccess) return fail(ILQR_ERR_HIP, "sensor vector launch failed");
+    return ILQR_OK;
+}
+
+// every pointer a device pointer on h's device (yhat, innovation, nis, first_bad: or null)
+static int sensor_update_launch(ilqr_handle* h, int32_t ny, int32_t per_instance_H, const double* H, const double* r, const double* y,
+                                const double* yhat, double* xhat, double* P, double* innovation, double* nis, int32_t* first_bad) {
+    if (!h->vt->launch_sensor_update) return fail(ILQR_ERR_MODEL, "this model module has no linear sensor kernel");
+    ilqr::SensorArgs a = {};
+    a.B = h->B; a.ny = ny; a.h_stride = per_instance_H ? (long long)ny * h->L.nx : 0; a.H = H; a.r = r; a.y = y; a.yhat = yhat; a.xhat = xhat; a.P = P;
+    a.innovation = innovation; a.nis = nis; a.first_bad = first_bad;
+    if (h->vt->launch_sensor_update(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "linear sensor update launch failed");
+    return ILQR_OK;
+}
+
+// H [ny][nx], sigma_y (or null), x, y: device pointers on h's device
+static int measure_linear_launch(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, int32_t ny, const double* H,
+                                 const double* sigma_y, const double* x, double* y) {
+    if (!h->vt->launch_plant_measure_linear) return fail(ILQR_ERR_MODEL, "this model module has no linear sensor kernel");
+    ilqr::SensorArgs a = {};
+    a.B = h->B; a.ny = ny; a.H = H; a.sigma = sigma_y; a.step = step; a.seed = seed; a.b0 = first_instance; a.x = x; a.y_out = y;
+    if (h->vt->launch_plant_measure_linear(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "linear measurement launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_estimate_update_linear_device(ilqr_handle* h, int32_t ny, int32_t per_instance_H, const double* H, const double* r, const double* y,
+                                       const double* yhat, double* xhat, double* P, double* innovation, double* nis, int32_t* first_bad) {
+    if (!H || !r || !y || !xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update_linear_device: null H, r, y, xhat or P");
+    ILQR_TRY(sensor_check(h, ny, per_instance_H, nullptr, r, nullptr, "ilqr_estimate_update_linear_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_estimate_update_linear");
+    HIP_TRY(hipSetDevice(h->device));
+    ILQR_TRY(sensor_vector_upload(h, h->plant[SENS_R], r, ny));
+    return sensor_update_launch(h, ny, per_instance_H, H, (const double*)h->plant[SENS_R].p, y, yhat, xhat, P, innovation, nis, first_bad);
+}
+
+int ilqr_estimate_update_linear(ilqr_handle* h, int32_t ny, int32_t per_instance_H, const double* H, const double* r, const double* y,
+                                const double* yhat, double* xhat, double* P, double* innovation, double* nis, int32_t* first_bad) {
+    if (!H || !r || !y || !xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update_linear: null H, r, y, xhat or P");
+    ILQR_TRY(sensor_check(h, ny, per_instance_H, H, r, nullptr, "ilqr_estimate_update_linear"));
+    const size_t n = (size_t)h->L.nx, m = (size_t)ny;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_estimate_update_linear(s, ny, per_instance_H, per_instance_H ? H + lo * m * n : H, r, y + lo * m, at(yhat, lo * m), xhat + lo * n,
+                                           P + lo * n * n, at(innovation, lo * m), at(nis, lo), at(first_bad, lo)); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t B = (size_t)h->B;
+    const Staged s_H = staged_in(h->plant[SENS_H], H, (per_instance_H ? B : 1) * m * n * 8);
+    const Staged s_r = staged_in(h->plant[SENS_R], r, m * 8);
+    const Staged s_y = staged_in(h->plant[EST_Y], y, B * m * 8);
+    const Staged s_yhat = staged_in(h->plant[SENS_YHAT], yhat, B * m * 8);
+    const Staged s_x = {&h->plant[PLANT_XC], xhat, xhat, B * n * 8};           // the estimate and its covariance go in and come back
+    const Staged s_P = {&h->plant[EST_P], P, P, B * n * n * 8};
+    const Staged s_inn = staged_out(h->plant[EST_INNOVATION], innovation, B * m * 8);
+    const Staged s_nis = staged_out(h->plant[EST_NIS], nis, B * 8);
+    const Staged s_bad = staged_out(h->plant[EST_FIRST_BAD], first_bad, B * 4);
+    const auto arrays = {s_H, s_r, s_y, s_yhat, s_x, s_P, s_inn, s_nis, s_bad};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(sensor_update_launch(h, ny, per_instance_H, s_H.dev<const double>(), s_r.dev<const double>(), s_y.dev<const double>(),
+                                  s_yhat.dev<const double>(), s_x.dev<double>(), s_P.dev<double>(), s_inn.dev<double>(), s_nis.dev<double>(),
+                                  s_bad.dev<int32_t>()));
+    return stage_out(h, arrays);
+}
+
+int ilqr_plant_measure_linear_device(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, int32_t ny, const double* H,
+                                     const double* sigma_y, const double* x, double* y) {
+    if (!H || !x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_linear_device: null H, x or y");
+    if (ny < 1 || ny > ilqr::SENSOR_MAX_NY) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_linear_device: ny must lie in 1 .. 64");
+    ILQR_TRY(sigma_check(sigma_y, ny, "ilqr_plant_measure_linear_device", "sigma_y"));
+    ILQR_TRY(measure_check(h, first_instance, step, nullptr, "ilqr_plant_measure_linear_device"));
+    ILQR_TRY(sensor_check(h, ny, 0, nullptr, nullptr, sigma_y, "ilqr_plant_measure_linear_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_plant_measure_linear");
+    HIP_TRY(hipSetDevice(h->device));
+    if (sigma_y) ILQR_TRY(sensor_vector_upload(h, h->plant[SENS_SIGMA], sigma_y, ny));
+    return measure_linear_launch(h, seed, first_instance, step, ny, H, sigma_y ? (const double*)h->plant[SENS_SIGMA].p : nullptr, x, y);
+}
+
+int ilqr_plant_measure_linear(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, int32_t ny, const double* H,
+                              const double* sigma_y, const double* x, double* y) {
+    if (!H || !x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_linear: null H, x or y");
+    if (ny < 1 || ny > ilqr::SENSOR_MAX_NY) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_linear: ny must lie in 1 .. 64");
+    ILQR_TRY(sigma_check(sigma_y, ny, "ilqr_plant_measure_linear", "sigma_y"));
+    ILQR_TRY(measure_check(h, first_instance, step, nullptr, "ilqr_plant_measure_linear"));
+    ILQR_TRY(sensor_check(h, ny, 0, H, nullptr, sigma_y, "ilqr_plant_measure_linear"));
+    const size_t n = (size_t)h->L.nx, m = (size_t)ny;
+    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        return ilqr_plant_measure_linear(s, seed, first_instance + (int64_t)lo, step, ny, H, sigma_y, x + lo * n, y + lo * m); }, true);
+    HIP_TRY(hipSetDevice(h->device));
+    const Staged s_H = staged_in(h->plant[SENS_H], H, m * n * 8);
+    const Staged s_sigma = staged_in(h->plant[SENS_SIGMA], sigma_y, m * 8);
+    const Staged s_x = staged_in(h->plant[PLANT_X], x, (size_t)h->B * n * 8);
+    const Staged s_y = staged_out(h->plant[PLANT_Y], y, (size_t)h->B * m * 8);
+    const auto arrays = {s_H, s_sigma, s_x, s_y};
+    ILQR_TRY(stage_in(h, arrays));
+    ILQR_TRY(measure_linear_launch(h, seed, first_instance, step, ny, s_H.dev<const double>(), s_sigma.dev<const double>(), s_x.dev<const double>(),
+                                   s_y.dev<double>()));
+    return stage_out(h, arrays);
+}
+
 // ---- the closed MPC loop, enqueued once: per period plant step, score, horizon shift, dual shift, solve, log row
 static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
 // everything its constituents refuse for these arguments, before any launch
 // The seam between plant and controller is in use: limits, measurement noise, a delay, or one of the two outputs that report on it.
 // Otherwise the loop hands the shift the plant state itself: no launch, no buffer and no argument of it differs from ilqr_mpc_run's.
-static bool mpc_measured(const ilqr_plant_io* io, const double* y_cl, const int32_t* saturated, const ilqr_estimator* est = nullptr) {
-    return (io && (io->u_min || io->u_max || io->sigma_y || io->delay)) || y_cl || saturated || est;
+static bool mpc_measured(const ilqr_plant_io* io, const double* y_cl, const int32_t* saturated, const ilqr_estimator* est = nullptr,
+                         const ilqr_sensor* sens = nullptr) {
+    return (io && (io->u_min || io->u_max || io->sigma_y || io->delay)) || y_cl || saturated || est || sens;
 }
 // measured: the run goes through the measurement slot (mpc_measured)
 static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, bool measured, const double* w_plant,
                      const double* w_preview, const double* cl_cost, const double* cl_violation, const ilqr_estimator* est, const double* xhat0,
-                     const double* Pcov, const double* xhat_cl, const double* pdiag_cl, const double* nis_cl, const char* who) {
+                     const double* Pcov, const double* xhat_cl, const double* pdiag_cl, const double* nis_cl, const ilqr_sensor* sens,
+                     const char* who) {
     const std::string me(who);
     if (!d) return fail(ILQR_ERR_INVALID, me + ": null descriptor");
-    if (!est && (xhat0 || Pcov || xhat_cl || pdiag_cl || nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
+    if (sens) {                                    // the linear sensor in the estimator's place; what needs no handle, as its calls order it
+        if (!Pcov) return fail(ILQR_ERR_INVALID, me + ": a sensor with a null P");
+        if (io && io->sigma_y) return fail(ILQR_ERR_INVALID, me + ": io->sigma_y together with a sensor: the sensor's own sigma_y [ny] replaces it");
+        if (!sens->H || !sens->r) return fail(ILQR_ERR_INVALID, me + ": null H or r");
+        if (sens->ny < 1 || sens->ny > ilqr::SENSOR_MAX_NY) return fail(ILQR_ERR_INVALID, me + ": ny must lie in 1 .. 64");
+        ILQR_TRY(variance_check(nullptr, sens->q, nullptr, 1, me));
+        for (int j = 0; j < sens->ny; ++j)
+            if (!(sens->r[j] > 0.0) || !std::isfinite(sens->r[j])) return fail(ILQR_ERR_INVALID, me + ": r must be finite and > 0");
+        ILQR_TRY(sigma_check(sens->sigma_y, sens->ny, me, "sigma_y"));
+    }
+    if (!est && !sens && (xhat0 || Pcov || xhat_cl || pdiag_cl || nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
     if (est && !Pcov) return fail(ILQR_ERR_INVALID, me + ": an estimator with a null P");
     if (est) {                                     // what needs no handle, as the two estimator calls order it
         if (!est->r) return fail(ILQR_ERR_INVALID, me + ": null r");
@@ -1739,6 +1886,10 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_pl
         ILQR_TRY(duals_check(h, d->steps, d->duals_tail, d->duals_penalty, who));
     }
     if (est) ILQR_TRY(variance_check(est->measured, est->q, est->r, h->L.nx, me));
+    if (sens) {
+        ILQR_TRY(variance_check(nullptr, sens->q, nullptr, h->L.nx, me));
+        ILQR_TRY(sensor_check(h, sens->ny, 0, sens->H, sens->r, sens->sigma_y, who));
+    }
     return ILQR_OK;
 }
 
@@ -1748,22 +1899,27 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_pl
 static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const double* x0, const double* w_plant, const double* w_preview,
                    double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
                    int32_t* saturated, const char* who, const ilqr_estimator* est = nullptr, const double* xhat0 = nullptr, double* Pcov = nullptr,
-                   double* xhat_cl = nullptr, double* pdiag_cl = nullptr, double* nis_cl = nullptr) {
-    const bool measured = mpc_measured(io, y_cl, saturated, est);
-    ILQR_TRY(mpc_check(h, d, io, measured, w_plant, w_preview, cl_cost, cl_violation, est, xhat0, Pcov, xhat_cl, pdiag_cl, nis_cl, who));
+                   double* xhat_cl = nullptr, double* pdiag_cl = nullptr, double* nis_cl = nullptr, const ilqr_sensor* sens = nullptr) {
+    const bool measured = mpc_measured(io, y_cl, saturated, est, sens);
+    ILQR_TRY(mpc_check(h, d, io, measured, w_plant, w_preview, cl_cost, cl_violation, est, xhat0, Pcov, xhat_cl, pdiag_cl, nis_cl, sens, who));
+    const bool filt = est || sens;                 // a filter stands between the measurement and the controller
+    const double* fq = est ? est->q : sens ? sens->q : nullptr;
+    const size_t ym_n = sens ? (size_t)sens->ny : (size_t)h->L.nx;           // the numbers of one measurement
     const size_t P = (size_t)d->periods, k = (size_t)d->steps, R = P * k, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
         ilqr_mpc_desc sd = *d;
         sd.first_instance += (int64_t)lo;
         return mpc_run(s, &sd, io, at(x0, lo * n), at(w_plant, lo * R * nwu), at(w_preview, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
-                       at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), at(y_cl, lo * P * n),
+                       at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), at(y_cl, lo * P * ym_n),
                        at(saturated, lo), who, est, at(xhat0, lo * n), at(Pcov, lo * n * n), at(xhat_cl, lo * P * n), at(pdiag_cl, lo * P * n),
-                       at(nis_cl, lo * P)); }, true);
+                       at(nis_cl, lo * P), sens); }, true);
     if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
     const bool score = cl_cost != nullptr;
     if (score && !h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
     if (measured && !h->vt->launch_plant_measure) return fail(ILQR_ERR_MODEL, "this model module has no measurement kernel");
     if (est && (!h->vt->launch_estimate_predict || !h->vt->launch_estimate_update)) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
+    if (sens && (!h->vt->launch_estimate_predict || !h->vt->launch_sensor_update || !h->vt->launch_plant_measure_linear))
+        return fail(ILQR_ERR_MODEL, "this model module has no linear sensor kernel");
     HIP_TRY(hipSetDevice(h->device));
     const size_t B = (size_t)h->B;
     const Staged s_x = staged_in(h->plant[PLANT_X], x0, B * n * 8);
@@ -1775,15 +1931,19 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
     const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
     const Staged s_cost = staged_out(h->plant[PLANT_COST], cl_cost, B * R * 8);
     const Staged s_viol = staged_out(h->plant[PLANT_VIOL], cl_violation, B * R * 8);
-    const Staged s_y_cl = staged_out(h->plant[PLANT_Y], y_cl, B * P * n * 8);
+    const Staged s_y_cl = staged_out(h->plant[PLANT_Y], y_cl, B * P * ym_n * 8);
     const Staged s_saturated = staged_out(h->plant[PLANT_SATURATED], saturated, B * 4);
     const Staged s_xhat0 = staged_in(h->plant[PLANT_XC], xhat0, B * n * 8);
     const Staged s_P = {&h->plant[EST_P], Pcov, Pcov, Pcov ? B * n * n * 8 : 0};          // P0 goes in, the last covariance comes back
     const Staged s_xhat_cl = staged_out(h->plant[EST_XHAT_CL], xhat_cl, B * P * n * 8);
     const Staged s_pdiag_cl = staged_out(h->plant[EST_PDIAG_CL], pdiag_cl, B * P * n * 8);
     const Staged s_nis_cl = staged_out(h->plant[EST_NIS_CL], nis_cl, B * P * 8);
+    // the sensor's H, r and sigma_y: copied once, before the first launch (the call synchronises before it returns)
+    const Staged s_sens_H = staged_in(h->plant[SENS_H], sens ? sens->H : nullptr, ym_n * n * 8);
+    const Staged s_sens_r = staged_in(h->plant[SENS_R], sens ? sens->r : nullptr, ym_n * 8);
+    const Staged s_sens_sigma = staged_in(h->plant[SENS_SIGMA], sens ? sens->sigma_y : nullptr, ym_n * 8);
     const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol, s_y_cl, s_saturated, s_xhat0, s_P, s_xhat_cl, s_pdiag_cl,
-                         s_nis_cl};
+                         s_nis_cl, s_sens_H, s_sens_r, s_sens_sigma};
     // Every buffer of the run exists before its first launch — the plant state also without an x0, what the shift would allocate
     // in its first call, the closed-loop trajectory the score reads even when the caller does not ask for it, and the controller's
     // state of a measured run — so that nothing between the first plant launch and the synchronise at the end waits for the device.
@@ -1795,8 +1955,8 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
         ILQR_TRY(grow(h, h->plant[PLANT_U_OUT], B * R * m * 8));
     }
     if (measured) ILQR_TRY(grow(h, h->plant[PLANT_XC], B * n * 8));
-    if (est) {                                     // the period's measurement and nis
-        ILQR_TRY(grow(h, h->plant[EST_Y], B * n * 8));
+    if (filt) {                                    // the period's measurement and nis
+        ILQR_TRY(grow(h, h->plant[EST_Y], B * ym_n * 8));
         ILQR_TRY(grow(h, h->plant[EST_NIS], B * 8));
     }
     ILQR_TRY(stage_in(h, arrays));
@@ -1811,16 +1971,27 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
     if (!x0) HIP_TRY(hipMemcpy2DAsync(xp, n * 8, h->ws + h->L.xb, (size_t)h->L.stride * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
     if (s_nonfinite.bytes) HIP_TRY(hipMemsetAsync(s_nonfinite.st->p, 0xff, B * 4, h->stream));       // -1: the plant kernel keeps the first mark
     if (s_saturated.bytes) HIP_TRY(hipMemsetAsync(s_saturated.st->p, 0, B * 4, h->stream));          // the plant kernel adds to it
-    double* ym = est ? (double*)h->plant[EST_Y].p : xc;                  // where the measurement lands: with a filter xc is the estimate
-    double* d_nis = est ? (double*)h->plant[EST_NIS].p : nullptr;
+    double* ym = filt ? (double*)h->plant[EST_Y].p : xc;                 // where the measurement lands: with a filter xc is the estimate
+    double* d_nis = filt ? (double*)h->plant[EST_NIS].p : nullptr;
+    // the measurement at plant step `step` and the update with it: the selection of state components, or the linear sensor
+    const auto measure = [&](int32_t step, double* y) {
+        return sens ? measure_linear_launch(h, d->seed, d->first_instance, step, sens->ny, s_sens_H.dev<const double>(), s_sens_sigma.dev<const double>(),
+                                            xp, y)
+                    : measure_launch(h, d->seed, d->first_instance, step, sigma_y, xp, y);
+    };
+    const auto update = [&]() {
+        return sens ? sensor_update_launch(h, sens->ny, 0, s_sens_H.dev<const double>(), s_sens_r.dev<const double>(), ym, nullptr, xc,
+                                           s_P.dev<double>(), nullptr, d_nis, nullptr)
+                    : update_launch(h, est->measured, est->r, ym, xc, s_P.dev<double>(), nullptr, d_nis, nullptr);
+    };
     const bool est_log = s_xhat_cl.bytes || s_pdiag_cl.bytes || s_nis_cl.bytes;
-    if (est && !xhat0) HIP_TRY(hipMemcpyAsync(xc, xp, B * n * 8, hipMemcpyDeviceToDevice, h->stream));              // x̂_0 = the first plant state
+    if (filt && !xhat0) HIP_TRY(hipMemcpyAsync(xc, xp, B * n * 8, hipMemcpyDeviceToDevice, h->stream));              // x̂_0 = the first plant state
     for (int32_t p = 0; p < d->periods; ++p) {
-        if (delayed && est) {
+        if (delayed && filt) {
             // the measurement of the state at p·k corrects the estimate, which then moves on to (p+1)·k under the plan in flight
-            ILQR_TRY(measure_launch(h, d->seed, d->first_instance, p * d->steps, sigma_y, xp, ym));
-            ILQR_TRY(update_launch(h, est->measured, est->r, ym, xc, s_P.dev<double>(), nullptr, d_nis, nullptr));
-            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, est->q, xc, s_P.dev<double>()));
+            ILQR_TRY(measure(p * d->steps, ym));
+            ILQR_TRY(update());
+            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, fq, xc, s_P.dev<double>()));
         } else if (delayed) {
             // the solve of this period started one period ago: from a measurement of the state at p·k, moved on by the controller's
             // own model under the plan in flight — same feedback and limits, no process noise, the handle's parameters, no outputs
@@ -1835,13 +2006,13 @@ static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* 
         a.w_ld = (long long)R; a.x_ld = (long long)R + 1; a.u_ld = (long long)R;                     // rows p·k .. of the run's arrays
         a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
         if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
-        if (measured && !delayed) ILQR_TRY(measure_launch(h, d->seed, d->first_instance, (p + 1) * d->steps, sigma_y, xp, ym));
-        if (est && !delayed) {                     // the estimate moves on to (p+1)·k under the plan in flight, then takes the measurement in
-            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, est->q, xc, s_P.dev<double>()));
-            ILQR_TRY(update_launch(h, est->measured, est->r, ym, xc, s_P.dev<double>(), nullptr, d_nis, nullptr));
+        if (measured && !delayed) ILQR_TRY(measure((p + 1) * d->steps, ym));
+        if (filt && !delayed) {                    // the estimate moves on to (p+1)·k under the plan in flight, then takes the measurement in
+            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, fq, xc, s_P.dev<double>()));
+            ILQR_TRY(update());
         }
         if (s_y_cl.bytes)                          // row p of y_cl: what the controller is given, with a filter the measurement taken
-            HIP_TRY(hipMemcpy2DAsync(s_y_cl.dev<double>() + (size_t)p * n, P * n * 8, ym, n * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpy2DAsync(s_y_cl.dev<double>() + (size_t)p * ym_n, P * ym_n * 8, ym, ym_n * 8, ym_n * 8, B, hipMemcpyDeviceToDevice, h->stream));
         if (est_log) {
             const unsigned grid = (unsigned)((B * n + 255) / 256);
             hipLaunchKernelGGL(estimate_log_kernel, dim3(grid), dim3(256), 0, h->stream, (int)B, (int)n, d->periods, p, xc, s_P.dev<double>(), d_nis,
@@ -1888,6 +2059,14 @@ int ilqr_mpc_run_est(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io
                      double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl, double* pdiag_cl, double* nis_cl) {
     return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_est", est,
                    xhat0, P, xhat_cl, pdiag_cl, nis_cl);
+}
+
+int ilqr_mpc_run_sensor(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const ilqr_sensor* sensor, const double* x0,
+                        const double* xhat0, double* P, const double* w_plant, const double* w_preview, double* x_cl, double* u_cl, double* log,
+                        int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl,
+                        double* pdiag_cl, double* nis_cl) {
+    return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_sensor",
+                   nullptr, xhat0, P, xhat_cl, pdiag_cl, nis_cl, sensor);
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

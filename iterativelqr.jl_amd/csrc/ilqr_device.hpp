@@ -2332,10 +2332,11 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_plant.hpp"
 #include "ilqr_device_score.hpp"
 #include "ilqr_device_estimate.hpp"
+#include "ilqr_device_sensor.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
-#define ILQR_MODEL_ABI_VERSION 20   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
+#define ILQR_MODEL_ABI_VERSION 21   /* bump whenever KArgs, Layout or this struct change: stale model modules are refused */
 extern "C" struct ilqr_model_vtable {
     int abi_version;     // ILQR_MODEL_ABI_VERSION the module was compiled against
     int kargs_bytes;     // sizeof(ilqr::KArgs) it was compiled against
@@ -2375,6 +2376,10 @@ extern "C" struct ilqr_model_vtable {
     int (*launch_plant_score)(const ilqr::ScoreArgs* a, void* stream);
     // what the controller is given of a plant state: a copy, or the state plus measurement noise (ilqr_device_plant.hpp)
     int (*launch_plant_measure)(const ilqr::MeasureArgs* a, void* stream);
+    // a linear sensor y = H x + v with ny outputs: the measurement itself, and the filter's measurement update with it
+    // (ilqr_device_sensor.hpp)
+    int (*launch_plant_measure_linear)(const ilqr::SensorArgs* a, void* stream);
+    int (*launch_sensor_update)(const ilqr::SensorArgs* a, void* stream);
     // the extended Kalman filter between sensor and controller: time update under the head of the plan, measurement update; both
     // read the workspace only (ilqr_device_estimate.hpp)
     int (*launch_estimate_predict)(const ilqr::EstArgs* a, void* stream);
@@ -2441,6 +2446,7 @@ struct ModelModule {
                                              packed1_lds<M>(), packed2_lds<M>(), &launch_policy_rollout<M>,
                                              &launch_candidates<M>, &launch_shift<M>, &launch_sample_candidates<M>, &launch_shift_duals<M>,
                                              &launch_plant<M>, &launch_mpc_log<M>, &launch_plant_score<M>, &launch_plant_measure<M>,
+                                             &launch_plant_measure_linear<M>, &launch_sensor_update<M>,
                                              &launch_estimate_predict<M>, &launch_estimate_update<M>};
         return &vt;
     }

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO, estimate_predict!, estimate_update!, mpc_run_est!, Estimator,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO, estimate_predict!, estimate_update!, mpc_run_est!, Estimator, estimate_update_linear!, plant_measure_linear!, mpc_run_sensor!, Sensor,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
 
 import Libdl
@@ -526,6 +526,99 @@ function mpc_run_est!(s::Solver, r::Vector{Float64}, P0::Array{Float64,3}; perio
                                Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
                                Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                     s.handle, d, io, est, x0 === nothing ? nul : x0, xhat0 === nothing ? nul : xhat0, P0, nul, nul, x, u, log, nf, nul, nul, y_cl,
+                    saturated, xhat, pdiag, nis))
+    end
+    return x, u, log, nf, y_cl, saturated, xhat, pdiag, nis, P0
+end
+
+# The measurement update with a linear sensor y = H x + v, v ~ N(0, diag(r)) (ilqr_estimate_update_linear): H :: (nx, ny) shared by the
+# batch or (nx, ny, B) one per instance (column-major here is the header's row-major [ny][nx]), y :: (ny, B), r :: ny, yhat :: (ny, B)
+# the caller's h(x̂) of a nonlinear sensor linearised at x̂. xhat and P are updated in place. Returns (innovation :: (ny, B), nis :: B,
+# first_bad :: B).
+function estimate_update_linear!(s::Solver, xhat::Matrix{Float64}, P::Array{Float64,3}, y::Matrix{Float64}, H::Array{Float64}, r::Vector{Float64};
+                                 yhat::Union{Nothing,Matrix{Float64}} = nothing)
+    ny = size(H, 2)
+    @assert size(xhat) == (s.nx, s.B) && size(P) == (s.nx, s.nx, s.B) && size(y) == (ny, s.B) && length(r) == ny
+    @assert size(H) == (s.nx, ny) || size(H) == (s.nx, ny, s.B)
+    @assert yhat === nothing || size(yhat) == (ny, s.B)
+    innovation = Matrix{Float64}(undef, ny, s.B)
+    nis = Vector{Float64}(undef, s.B)
+    first_bad = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_estimate_update_linear, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}),
+                s.handle, Int32(ny), Int32(ndims(H) == 3 ? 1 : 0), H, r, y, yhat === nothing ? Ptr{Float64}(C_NULL) : yhat, xhat, P, innovation, nis,
+                first_bad))
+    return innovation, nis, first_bad
+end
+
+# What a linear sensor reads of the plant states x :: (nx, B) (ilqr_plant_measure_linear): y = H x with H :: (nx, ny), plus sigma_y[j] · z
+# from plant_measure!'s stream. Returns y :: (ny, B).
+function plant_measure_linear!(s::Solver, x::Matrix{Float64}, H::Matrix{Float64}; step::Integer = 0,
+                               sigma_y::Union{Nothing,Vector{Float64}} = nothing, seed::Integer = 0, first_instance::Integer = 0)
+    ny = size(H, 2)
+    @assert size(x) == (s.nx, s.B) && size(H, 1) == s.nx && (sigma_y === nothing || length(sigma_y) == ny)
+    y = Matrix{Float64}(undef, ny, s.B)
+    check(ccall((:ilqr_plant_measure_linear, LIB[]), Cint,
+                (Ptr{Cvoid}, UInt64, Int64, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                s.handle, UInt64(seed), Int64(first_instance), Int32(step), Int32(ny), H, sigma_y === nothing ? Ptr{Float64}(C_NULL) : sigma_y, x, y))
+    return y
+end
+
+# ilqr_sensor, field for field
+struct Sensor
+    ny::Int32
+    reserved::Int32
+    H::Ptr{Float64}
+    r::Ptr{Float64}
+    q::Ptr{Float64}
+    sigma_y::Ptr{Float64}
+end
+
+# mpc_run_est! with the linear sensor in the place of the selection of state components (ilqr_mpc_run_sensor): H :: (nx, ny), r and
+# sigma_y :: ny. Returns (x, u, log, first_nonfinite, y_cl :: (ny, periods, B), saturated, xhat, pdiag, nis, P0). (The symbol is looked
+# up by hand, as mpc_run_io!'s.)
+function mpc_run_sensor!(s::Solver, H::Matrix{Float64}, r::Vector{Float64}, P0::Array{Float64,3}; periods::Integer, steps::Integer = 1,
+                         plant_feedback::Bool = false, shift_feedback::Bool = false, shift_tail::Symbol = :hold, warm::Bool = true,
+                         duals_tail::Symbol = :hold, duals_penalty::Symbol = :keep, seed::Integer = 0, first_instance::Integer = 0,
+                         sigma_x::Union{Nothing,Vector{Float64}} = nothing, x0::Union{Nothing,Matrix{Float64}} = nothing,
+                         xhat0::Union{Nothing,Matrix{Float64}} = nothing, u_min::Union{Nothing,Vector{Float64}} = nothing,
+                         u_max::Union{Nothing,Vector{Float64}} = nothing, sigma_y::Union{Nothing,Vector{Float64}} = nothing, delay::Integer = 0,
+                         q::Union{Nothing,Vector{Float64}} = nothing)
+    ny = size(H, 2)
+    @assert periods >= 1 && 1 <= steps <= s.T - 1 && (delay == 0 || delay == 1)
+    @assert size(H, 1) == s.nx && length(r) == ny && size(P0) == (s.nx, s.nx, s.B) && (q === nothing || length(q) == s.nx)
+    @assert sigma_y === nothing || length(sigma_y) == ny
+    @assert (x0 === nothing || size(x0) == (s.nx, s.B)) && (xhat0 === nothing || size(xhat0) == (s.nx, s.B))
+    R = periods * steps
+    nul = Ptr{Float64}(C_NULL)
+    x = Array{Float64,3}(undef, s.nx, R + 1, s.B)
+    u = Array{Float64,3}(undef, s.nu, R, s.B)
+    log = Array{Float64,3}(undef, 9, periods, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    y_cl = Array{Float64,3}(undef, ny, periods, s.B)
+    saturated = Vector{Int32}(undef, s.B)
+    xhat = Array{Float64,3}(undef, s.nx, periods, s.B)
+    pdiag = Array{Float64,3}(undef, s.nx, periods, s.B)
+    nis = Matrix{Float64}(undef, periods, s.B)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    sig = sigma_x === nothing ? Float64[] : sigma_x
+    lo = u_min === nothing ? Float64[] : u_min
+    hi = u_max === nothing ? Float64[] : u_max
+    sy = sigma_y === nothing ? Float64[] : sigma_y
+    qq = q === nothing ? Float64[] : q
+    GC.@preserve sig lo hi sy qq r H begin
+        d = MpcDesc(Int32(periods), Int32(steps), Int32(plant_feedback ? 1 : 0), Int32(shift_feedback ? 1 : 0),
+                    Int32(shift_tail === :hold ? 0 : 1), Int32(warm ? 1 : 0), Int32(duals_tail === :hold ? 0 : 1),
+                    Int32(duals_penalty === :keep ? 0 : 1), UInt64(seed), Int64(first_instance),
+                    sigma_x === nothing ? nul : pointer(sig))
+        io = PlantIO(u_min === nothing ? nul : pointer(lo), u_max === nothing ? nul : pointer(hi), nul, Int32(delay), Int32(0))
+        sensor = Sensor(Int32(ny), Int32(0), pointer(H), pointer(r), q === nothing ? nul : pointer(qq), sigma_y === nothing ? nul : pointer(sy))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_mpc_run_sensor)
+        check(ccall(fn, Cint, (Ptr{Cvoid}, Ref{MpcDesc}, Ref{PlantIO}, Ref{Sensor}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, d, io, sensor, x0 === nothing ? nul : x0, xhat0 === nothing ? nul : xhat0, P0, nul, nul, x, u, log, nf, nul, nul, y_cl,
                     saturated, xhat, pdiag, nis))
     end
     return x, u, log, nf, y_cl, saturated, xhat, pdiag, nis, P0
