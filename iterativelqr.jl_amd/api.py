@@ -32,6 +32,16 @@ def _p(a):
     return a.ctypes.data_as(_ffi.c_double_p)
 
 
+def _nul(a):
+    """a float64 array as a pointer, None as a null pointer"""
+    return _p(a) if a is not None else None
+
+
+def _vp(p):
+    """a raw device pointer, None (or 0) as a null pointer"""
+    return C.c_void_p(p) if p else None
+
+
 def _limits(nu, u_min, u_max):
     """the actuator's limits as contiguous float64 vectors of nu entries (None stays None)"""
     out = []
@@ -251,10 +261,8 @@ class Solver:
     def initialize_rollout_candidates_device_(self, candidates, d_x1_ptr, d_u_ptr, violation_weight=0.0, d_chosen_ptr=None, d_cost_ptr=None,
                                               d_max_violation_ptr=None, d_first_nonfinite_ptr=None):
         """The same with raw device pointers on the handle's device (None = not wanted); asynchronous on the handle's stream."""
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _ffi.check(_ffi.lib().ilqr_initialize_rollout_candidates_device(self._h, int(candidates), float(violation_weight), vp(d_x1_ptr), vp(d_u_ptr),
-                                                                        vp(d_chosen_ptr), vp(d_cost_ptr), vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr)))
+        _ffi.check(_ffi.lib().ilqr_initialize_rollout_candidates_device(self._h, int(candidates), float(violation_weight), _vp(d_x1_ptr), _vp(d_u_ptr),
+                                                                        _vp(d_chosen_ptr), _vp(d_cost_ptr), _vp(d_max_violation_ptr), _vp(d_first_nonfinite_ptr)))
 
     _SAMPLE_MODES = {"pick": 0, "blend": 1}
 
@@ -290,7 +298,7 @@ class Solver:
             out["u"] = np.empty((self.B, S, self.T - 1, self.nu))
         _ffi.check(_ffi.lib().ilqr_sample_rollout_candidates(
             self._h, S, mode, int(seed), int(first_instance), _p(sigma), float(violation_weight), float(temperature),
-            _p(x1) if x1 is not None else None, _p(base_u) if base_u is not None else None, out["chosen"].ctypes.data_as(i32), _p(out["cost"]),
+            _nul(x1), _nul(base_u), out["chosen"].ctypes.data_as(i32), _p(out["cost"]),
             _p(out["max_violation"]), out["first_nonfinite"].ctypes.data_as(i32), _p(out["weights"]), _p(out["u"]) if return_candidates else None))
         return out
 
@@ -300,11 +308,9 @@ class Solver:
         """The same with raw device pointers on the handle's device (None = the resident input / not wanted); sigma stays a host
         array; asynchronous on the handle's stream."""
         sigma, S, mode = self._sample_arguments(sigma, candidates, mode)
-        def vp(p):
-            return C.c_void_p(p) if p else None
         _ffi.check(_ffi.lib().ilqr_sample_rollout_candidates_device(
-            self._h, S, mode, int(seed), int(first_instance), _p(sigma), float(violation_weight), float(temperature), vp(d_x1_ptr), vp(d_base_u_ptr),
-            vp(d_chosen_ptr), vp(d_cost_ptr), vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr), vp(d_weights_ptr), vp(d_u_out_ptr)))
+            self._h, S, mode, int(seed), int(first_instance), _p(sigma), float(violation_weight), float(temperature), _vp(d_x1_ptr), _vp(d_base_u_ptr),
+            _vp(d_chosen_ptr), _vp(d_cost_ptr), _vp(d_max_violation_ptr), _vp(d_first_nonfinite_ptr), _vp(d_weights_ptr), _vp(d_u_out_ptr)))
 
     _TAILS = {"hold": 0, "zero": 1}
 
@@ -331,15 +337,13 @@ class Solver:
             w_tail = np.ascontiguousarray(w_tail, dtype=np.float64)
             if self.num_user_parameter > 0 and steps > 0 and w_tail.shape != (self.B, steps, self.num_user_parameter):
                 raise ValueError("w_tail must have shape [B, steps, num_parameter]")
-        _ffi.check(_ffi.lib().ilqr_shift_horizon(self._h, steps, tail, 1 if feedback else 0, _p(x1) if x1 is not None else None,
-                                                 _p(w_tail) if w_tail is not None else None))
+        _ffi.check(_ffi.lib().ilqr_shift_horizon(self._h, steps, tail, 1 if feedback else 0, _nul(x1),
+                                                 _nul(w_tail)))
 
     def shift_horizon_device_(self, steps=1, d_x1_ptr=None, feedback=False, tail="hold", d_w_tail_ptr=None):
         """The same with raw device pointers on the handle's device (None = not given); asynchronous on the handle's stream."""
         steps, tail = self._shift_arguments(steps, tail)
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _ffi.check(_ffi.lib().ilqr_shift_horizon_device(self._h, steps, tail, 1 if feedback else 0, vp(d_x1_ptr), vp(d_w_tail_ptr)))
+        _ffi.check(_ffi.lib().ilqr_shift_horizon_device(self._h, steps, tail, 1 if feedback else 0, _vp(d_x1_ptr), _vp(d_w_tail_ptr)))
 
     _PENALTIES = {"keep": 0, "reset": 1}
 
@@ -402,13 +406,13 @@ class Solver:
         if u_min is not None or u_max is not None:
             out["saturated"] = np.empty(self.B, dtype=np.int32)
             _ffi.check(_ffi.lib().ilqr_plant_step_limited(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
-                                                          _p(sigma_x) if sigma_x is not None else None, _p(u_min) if u_min is not None else None,
-                                                          _p(u_max) if u_max is not None else None, _p(w_plant) if w_plant is not None else None,
+                                                          _nul(sigma_x), _nul(u_min),
+                                                          _nul(u_max), _nul(w_plant),
                                                           _p(x), _p(out["x"]), _p(out["u"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32)),
                                                           out["saturated"].ctypes.data_as(C.POINTER(C.c_int32))))
             return out
         _ffi.check(_ffi.lib().ilqr_plant_step(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
-                                              _p(sigma_x) if sigma_x is not None else None, _p(w_plant) if w_plant is not None else None, _p(x),
+                                              _nul(sigma_x), _nul(w_plant), _p(x),
                                               _p(out["x"]), _p(out["u"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
@@ -418,18 +422,16 @@ class Solver:
         place; sigma_x, u_min and u_max stay host arrays; asynchronous on the handle's stream."""
         steps, sigma_x, _ = self._plant_arguments(steps, sigma_x, None, int(steps))
         u_min, u_max = _limits(self.nu, u_min, u_max)
-        def vp(p):
-            return C.c_void_p(p) if p else None
         if u_min is not None or u_max is not None or d_saturated_ptr:
             _ffi.check(_ffi.lib().ilqr_plant_step_limited_device(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
-                                                                 _p(sigma_x) if sigma_x is not None else None,
-                                                                 _p(u_min) if u_min is not None else None, _p(u_max) if u_max is not None else None,
-                                                                 vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_x_out_ptr), vp(d_u_out_ptr),
-                                                                 vp(d_first_nonfinite_ptr), vp(d_saturated_ptr)))
+                                                                 _nul(sigma_x),
+                                                                 _nul(u_min), _nul(u_max),
+                                                                 _vp(d_w_plant_ptr), _vp(d_x_ptr), _vp(d_x_out_ptr), _vp(d_u_out_ptr),
+                                                                 _vp(d_first_nonfinite_ptr), _vp(d_saturated_ptr)))
             return
         _ffi.check(_ffi.lib().ilqr_plant_step_device(self._h, steps, 1 if feedback else 0, int(seed), int(first_instance), int(step0),
-                                                     _p(sigma_x) if sigma_x is not None else None, vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_x_out_ptr),
-                                                     vp(d_u_out_ptr), vp(d_first_nonfinite_ptr)))
+                                                     _nul(sigma_x), _vp(d_w_plant_ptr), _vp(d_x_ptr), _vp(d_x_out_ptr),
+                                                     _vp(d_u_out_ptr), _vp(d_first_nonfinite_ptr)))
 
     def plant_measure_(self, x, step=0, sigma_y=None, seed=0, first_instance=0):
         """What a controller is given of the plant states x [B, nx] (ilqr_plant_measure): y = x where sigma_y is None or zero, else
@@ -440,7 +442,7 @@ class Solver:
             raise ValueError("x must have shape [B, nx]")
         sigma_y = _sigma_y(self.nx, sigma_y)
         y = np.empty((self.B, self.nx))
-        _ffi.check(_ffi.lib().ilqr_plant_measure(self._h, int(seed), int(first_instance), int(step), _p(sigma_y) if sigma_y is not None else None,
+        _ffi.check(_ffi.lib().ilqr_plant_measure(self._h, int(seed), int(first_instance), int(step), _nul(sigma_y),
                                                  _p(x), _p(y)))
         return y
 
@@ -449,7 +451,7 @@ class Solver:
         asynchronous on the handle's stream."""
         sigma_y = _sigma_y(self.nx, sigma_y)
         _ffi.check(_ffi.lib().ilqr_plant_measure_device(self._h, int(seed), int(first_instance), int(step),
-                                                        _p(sigma_y) if sigma_y is not None else None, C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr)))
+                                                        _nul(sigma_y), C.c_void_p(d_x_ptr), C.c_void_p(d_y_ptr)))
 
     def _sensor(self, H, r=None, sigma_y=None, per_instance=True):
         """the linear sensor's arrays: H [ny, nx] (or, where allowed, [B, ny, nx]: one per instance), r and sigma_y [ny] (or scalars)"""
@@ -481,7 +483,7 @@ class Solver:
                 raise ValueError("yhat must have shape [B, ny]")
         out = dict(xhat=xhat, P=P, innovation=np.empty((self.B, ny)), nis=np.empty(self.B), first_bad=np.empty(self.B, dtype=np.int32))
         _ffi.check(_ffi.lib().ilqr_estimate_update_linear(self._h, ny, 1 if H.ndim == 3 else 0, _p(H), _p(r), _p(y),
-                                                          _p(yhat) if yhat is not None else None, _p(xhat), _p(P), _p(out["innovation"]),
+                                                          _nul(yhat), _p(xhat), _p(P), _p(out["innovation"]),
                                                           _p(out["nis"]), _i32p(out["first_bad"])))
         return out
 
@@ -491,11 +493,9 @@ class Solver:
         asynchronous on the handle's stream."""
         ny = int(ny)
         r = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64), (max(ny, 0),)))
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _ffi.check(_ffi.lib().ilqr_estimate_update_linear_device(self._h, ny, 1 if per_instance_H else 0, vp(d_H_ptr), _p(r), vp(d_y_ptr),
-                                                                 vp(d_yhat_ptr), vp(d_xhat_ptr), vp(d_P_ptr), vp(d_innovation_ptr), vp(d_nis_ptr),
-                                                                 vp(d_first_bad_ptr)))
+        _ffi.check(_ffi.lib().ilqr_estimate_update_linear_device(self._h, ny, 1 if per_instance_H else 0, _vp(d_H_ptr), _p(r), _vp(d_y_ptr),
+                                                                 _vp(d_yhat_ptr), _vp(d_xhat_ptr), _vp(d_P_ptr), _vp(d_innovation_ptr), _vp(d_nis_ptr),
+                                                                 _vp(d_first_bad_ptr)))
 
     def plant_measure_linear_(self, x, H, step=0, sigma_y=None, seed=0, first_instance=0):
         """What a linear sensor reads of the plant states x [B, nx] (ilqr_plant_measure_linear): y = H x with H [ny, nx], plus
@@ -507,7 +507,7 @@ class Solver:
         H, ny, _, sigma_y = self._sensor(H, None, sigma_y, per_instance=False)
         y = np.empty((self.B, ny))
         _ffi.check(_ffi.lib().ilqr_plant_measure_linear(self._h, int(seed), int(first_instance), int(step), ny, _p(H),
-                                                        _p(sigma_y) if sigma_y is not None else None, _p(x), _p(y)))
+                                                        _nul(sigma_y), _p(x), _p(y)))
         return y
 
     def plant_measure_linear_device_(self, d_x_ptr, d_y_ptr, d_H_ptr, ny, step=0, sigma_y=None, seed=0, first_instance=0):
@@ -518,7 +518,7 @@ class Solver:
             sigma_y = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_y, dtype=np.float64), (max(ny, 0),)))
         _ffi.check(_ffi.lib().ilqr_plant_measure_linear_device(self._h, int(seed), int(first_instance), int(step), ny,
                                                                C.c_void_p(d_H_ptr) if d_H_ptr else None,
-                                                               _p(sigma_y) if sigma_y is not None else None, C.c_void_p(d_x_ptr),
+                                                               _nul(sigma_y), C.c_void_p(d_x_ptr),
                                                                C.c_void_p(d_y_ptr)))
 
     def _estimate_arrays(self, xhat, P):
@@ -539,8 +539,7 @@ class Solver:
         u_min, u_max = _limits(self.nu, u_min, u_max)
         _, q, _ = _variances(self.nx, None, q, None)
         xhat, P = self._estimate_arrays(xhat, P)
-        nul = lambda a: _p(a) if a is not None else None
-        _ffi.check(_ffi.lib().ilqr_estimate_predict(self._h, steps, 1 if feedback else 0, nul(u_min), nul(u_max), nul(q), _p(xhat), _p(P)))
+        _ffi.check(_ffi.lib().ilqr_estimate_predict(self._h, steps, 1 if feedback else 0, _nul(u_min), _nul(u_max), _nul(q), _p(xhat), _p(P)))
         return xhat, P
 
     def estimate_predict_device_(self, d_xhat_ptr, d_P_ptr, steps=1, feedback=False, u_min=None, u_max=None, q=None):
@@ -549,8 +548,7 @@ class Solver:
         steps, _, _ = self._plant_arguments(steps, None, None, int(steps))
         u_min, u_max = _limits(self.nu, u_min, u_max)
         _, q, _ = _variances(self.nx, None, q, None)
-        nul = lambda a: _p(a) if a is not None else None
-        _ffi.check(_ffi.lib().ilqr_estimate_predict_device(self._h, steps, 1 if feedback else 0, nul(u_min), nul(u_max), nul(q),
+        _ffi.check(_ffi.lib().ilqr_estimate_predict_device(self._h, steps, 1 if feedback else 0, _nul(u_min), _nul(u_max), _nul(q),
                                                            C.c_void_p(d_xhat_ptr), C.c_void_p(d_P_ptr)))
 
     def estimate_update_(self, xhat, P, y, r, measured=None):
@@ -576,10 +574,8 @@ class Solver:
         measured, _, r = _variances(self.nx, measured, None, r)
         if r is None:
             raise ValueError("r must be given")
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _ffi.check(_ffi.lib().ilqr_estimate_update_device(self._h, _i32p(measured), _p(r), vp(d_y_ptr), vp(d_xhat_ptr), vp(d_P_ptr),
-                                                          vp(d_innovation_ptr), vp(d_nis_ptr), vp(d_first_bad_ptr)))
+        _ffi.check(_ffi.lib().ilqr_estimate_update_device(self._h, _i32p(measured), _p(r), _vp(d_y_ptr), _vp(d_xhat_ptr), _vp(d_P_ptr),
+                                                          _vp(d_innovation_ptr), _vp(d_nis_ptr), _vp(d_first_bad_ptr)))
 
     def plant_score_(self, x, u, w_plant=None):
         """The score of plant steps on the device (ilqr_plant_score): the realised stage cost and constraint violation of the states a
@@ -594,17 +590,15 @@ class Solver:
         if x.shape != (self.B, steps + 1, self.nx):
             raise ValueError("x must have shape [B, steps + 1, nx]")
         out = dict(cost=np.empty((self.B, steps)), violation=np.empty((self.B, steps)))
-        _ffi.check(_ffi.lib().ilqr_plant_score(self._h, steps, _p(w_plant) if w_plant is not None else None, _p(x), _p(u), _p(out["cost"]),
+        _ffi.check(_ffi.lib().ilqr_plant_score(self._h, steps, _nul(w_plant), _p(x), _p(u), _p(out["cost"]),
                                                _p(out["violation"])))
         return out
 
     def plant_score_device_(self, steps, d_x_ptr, d_u_ptr, d_cost_ptr, d_violation_ptr=None, d_w_plant_ptr=None):
         """The same with raw device pointers on the handle's device (None = not given / not wanted); asynchronous on the handle's
         stream."""
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _ffi.check(_ffi.lib().ilqr_plant_score_device(self._h, int(steps), vp(d_w_plant_ptr), vp(d_x_ptr), vp(d_u_ptr), vp(d_cost_ptr),
-                                                      vp(d_violation_ptr)))
+        _ffi.check(_ffi.lib().ilqr_plant_score_device(self._h, int(steps), _vp(d_w_plant_ptr), _vp(d_x_ptr), _vp(d_u_ptr), _vp(d_cost_ptr),
+                                                      _vp(d_violation_ptr)))
 
     def mpc_run_(self, periods, steps=1, x0=None, plant_feedback=False, shift_feedback=False, shift_tail="hold", warm=True, duals_tail="hold",
                  duals_penalty="keep", sigma_x=None, seed=0, first_instance=0, w_plant=None, w_preview=None, score=False, u_min=None, u_max=None,
@@ -675,48 +669,37 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_set_options(self._h, C.byref(self.options)))
         d = _ffi.MpcDesc(periods, steps, 1 if plant_feedback else 0, 1 if shift_feedback else 0, self._TAILS[shift_tail], 1 if warm else 0,
                          self._TAILS[duals_tail], self._PENALTIES[duals_penalty], int(seed), int(first_instance),
-                         _p(sigma_x) if sigma_x is not None else None)
+                         _nul(sigma_x))
         R = periods * steps
         x, u = np.empty((self.B, R + 1, self.nx)), np.empty((self.B, R, self.nu))
         log, nf = np.empty((self.B, periods, _ffi.MPC_LOG_W)), np.empty(self.B, dtype=np.int32)
         cl_cost, cl_violation = (np.empty((self.B, R)), np.empty((self.B, R))) if score else (None, None)
-        y_cl = saturated = None
-
-        def nul(a):
-            return _p(a) if a is not None else None
-        if estimator is not None:
-            pio = _ffi.PlantIO(nul(u_min), nul(u_max), nul(sigma_y), int(delay), 0)
+        y_cl = saturated = xhat = pdiag = nis = None
+        plant, preview = (_nul(x0), _nul(w_plant)), (_nul(w_preview),)
+        out, scores = (_p(x), _p(u), _p(log), _i32p(nf)), (_nul(cl_cost), _nul(cl_violation))
+        if estimator is not None or io:
+            pio = _ffi.PlantIO(_nul(u_min), _nul(u_max), _nul(sigma_y), int(delay), 0)
             y_cl, saturated = np.empty((self.B, periods, e_ny if linear else self.nx)), np.empty(self.B, dtype=np.int32)
+            seam = (_p(y_cl), _i32p(saturated))
+        # the plainest entry point that offers what was asked for, and its arguments behind the handle and the descriptor
+        if estimator is not None:
             xhat, pdiag, nis = np.empty((self.B, periods, self.nx)), np.empty((self.B, periods, self.nx)), np.empty((self.B, periods))
             if linear:
-                est = _ffi.Sensor(e_ny, 0, _p(e_H), _p(e_r), nul(e_q), nul(e_sigma))
-                run = _ffi.lib().ilqr_mpc_run_sensor
+                run, est = _ffi.lib().ilqr_mpc_run_sensor, _ffi.Sensor(e_ny, 0, _p(e_H), _p(e_r), _nul(e_q), _nul(e_sigma))
             else:
-                est = _ffi.Estimator(_i32p(e_measured), nul(e_q), _p(e_r))
-                run = _ffi.lib().ilqr_mpc_run_est
-            _ffi.check(run(self._h, C.byref(d), C.byref(pio), C.byref(est), nul(x0), nul(e_xhat0), _p(e_P), nul(w_plant),
-                           nul(w_preview), _p(x), _p(u), _p(log), _i32p(nf), nul(cl_cost), nul(cl_violation), _p(y_cl),
-                           _i32p(saturated), _p(xhat), _p(pdiag), _p(nis)))
-            ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
-            return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)},
-                             nf, cl_cost, cl_violation, y_cl, saturated, xhat, pdiag, nis, e_P)
-        if io:
-            pio = _ffi.PlantIO(nul(u_min), nul(u_max), nul(sigma_y), int(delay), 0)
-            y_cl, saturated = np.empty((self.B, periods, self.nx)), np.empty(self.B, dtype=np.int32)
-            _ffi.check(_ffi.lib().ilqr_mpc_run_io(self._h, C.byref(d), C.byref(pio), nul(x0), nul(w_plant), nul(w_preview), _p(x), _p(u), _p(log),
-                                                  nf.ctypes.data_as(C.POINTER(C.c_int32)), nul(cl_cost), nul(cl_violation), _p(y_cl),
-                                                  saturated.ctypes.data_as(C.POINTER(C.c_int32))))
-        elif w_preview is None and not score:
-            _ffi.check(_ffi.lib().ilqr_mpc_run(self._h, C.byref(d), _p(x0) if x0 is not None else None, _p(w_plant) if w_plant is not None else None,
-                                               _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32))))
+                run, est = _ffi.lib().ilqr_mpc_run_est, _ffi.Estimator(_i32p(e_measured), _nul(e_q), _p(e_r))
+            args = ((C.byref(pio), C.byref(est), _nul(x0), _nul(e_xhat0), _p(e_P), _nul(w_plant)) + preview + out + scores + seam
+                    + (_p(xhat), _p(pdiag), _p(nis)))
+        elif io:
+            run, args = _ffi.lib().ilqr_mpc_run_io, (C.byref(pio),) + plant + preview + out + scores + seam
+        elif w_preview is not None or score:
+            run, args = _ffi.lib().ilqr_mpc_run_preview, plant + preview + out + scores
         else:
-            _ffi.check(_ffi.lib().ilqr_mpc_run_preview(self._h, C.byref(d), _p(x0) if x0 is not None else None,
-                                                       _p(w_plant) if w_plant is not None else None, _p(w_preview) if w_preview is not None else None,
-                                                       _p(x), _p(u), _p(log), nf.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                       _p(cl_cost) if score else None, _p(cl_violation) if score else None))
+            run, args = _ffi.lib().ilqr_mpc_run, plant + out
+        _ffi.check(run(self._h, C.byref(d), *args))
         ints = ("iterations", "outer_iterations", "status", "potrf_info", "rollouts")
-        return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)}, nf,
-                         cl_cost, cl_violation, y_cl, saturated)
+        return MpcResult(x, u, {f: (log[:, :, c].astype(np.int32) if f in ints else log[:, :, c].copy()) for c, f in enumerate(_ffi.MPC_LOG_COLUMNS)},
+                         nf, cl_cost, cl_violation, y_cl, saturated, xhat, pdiag, nis, e_P if estimator is not None else None)
 
     def set_parameters_(self, w):
         """Solver(...; parameters=θ): w[b, t] is the parameter vector of timestep t of instance b."""
@@ -821,7 +804,7 @@ class Solver:
         out = dict(cost=np.empty((self.B, S)), max_violation=np.empty((self.B, S)), first_nonfinite=np.empty((self.B, S), dtype=np.int32))
         if trajectories:
             out["x"] = np.empty((self.B, S, self.T, self.nx)); out["u"] = np.empty((self.B, S, self.T - 1, self.nu))
-        _ffi.check(_ffi.lib().ilqr_rollout_policy(self._h, S, float(step_size), _p(x1), _p(w) if w is not None else None, _p(out["cost"]),
+        _ffi.check(_ffi.lib().ilqr_rollout_policy(self._h, S, float(step_size), _p(x1), _nul(w), _p(out["cost"]),
                                                   _p(out["max_violation"]), out["first_nonfinite"].ctypes.data_as(C.POINTER(C.c_int32)),
                                                   _p(out["x"]) if trajectories else None, _p(out["u"]) if trajectories else None))
         return out
@@ -829,10 +812,8 @@ class Solver:
     def rollout_policy_device(self, samples, d_x1_ptr, d_cost_ptr, d_w_ptr=None, step_size=0.0, d_max_violation_ptr=None,
                               d_first_nonfinite_ptr=None, d_x_ptr=None, d_u_ptr=None):
         """The same with raw device pointers on the handle's device (None = not wanted); asynchronous on the handle's stream."""
-        def vp(p):
-            return C.c_void_p(p) if p else None
-        _ffi.check(_ffi.lib().ilqr_rollout_policy_device(self._h, int(samples), float(step_size), vp(d_x1_ptr), vp(d_w_ptr), vp(d_cost_ptr),
-                                                         vp(d_max_violation_ptr), vp(d_first_nonfinite_ptr), vp(d_x_ptr), vp(d_u_ptr)))
+        _ffi.check(_ffi.lib().ilqr_rollout_policy_device(self._h, int(samples), float(step_size), _vp(d_x1_ptr), _vp(d_w_ptr), _vp(d_cost_ptr),
+                                                         _vp(d_max_violation_ptr), _vp(d_first_nonfinite_ptr), _vp(d_x_ptr), _vp(d_u_ptr)))
 
     def stream_ptr(self):
         """The handle's HIP stream as an integer (ilqr_get_stream), e.g. for torch.cuda.ExternalStream; not on a sharded handle."""

@@ -349,29 +349,72 @@ template <class T> int own_if_null(ilqr_handle* h, T*& out, ilqr_handle::Stage& 
     return ILQR_OK;
 }
 
-// One array of a host form: the stage that holds it on the device, the host array it is uploaded from (an input) or downloaded
-// to (an output), its size. An array the caller did not give has no bytes: it never allocates, and its device pointer is null.
+// One array of a host form: the stage that holds it on the device, the host array it is uploaded from (src) and / or downloaded to
+// (dst), its element size and its extent in elements — per instance, or (shared) of the one copy the whole batch reads. An array the
+// caller did not give has no bytes: it never allocates, and its device pointer is null — unless the form keeps it on the device all
+// the same (keep: a buffer of the call that nobody uploads or downloads). IN_RESIDENT: the handle's resident inputs, stage 0 = d_x1,
+// 1 = d_u, which never grow.
+enum StageSet { IN_POL, IN_CAND, IN_SHIFT, IN_SAMP, IN_PLANT, IN_RESIDENT };
 struct Staged {
-    ilqr_handle::Stage* st; const void* src; void* dst; size_t bytes;
-    template <class T> T* dev() const { return bytes ? (T*)st->p : nullptr; }
+    StageSet set; int stage; const void* src; void* dst; size_t elem, extent; bool shared, keep;
+    void* p; size_t bytes;                     // on the handle the form runs on (run_staged fills them in)
+    double* d() const { return (double*)p; }
+    int32_t* i() const { return (int32_t*)p; }
+    Staged kept(bool on) const { Staged s = *this; s.keep = on; return s; }
 };
-Staged staged_in(ilqr_handle::Stage& st, const void* src, size_t bytes) { return {&st, src, nullptr, src ? bytes : 0}; }
-Staged staged_out(ilqr_handle::Stage& st, void* dst, size_t bytes) { return {&st, nullptr, dst, dst ? bytes : 0}; }
+template <class T> Staged staged_in(StageSet set, int stage, const T* src, size_t extent) { return {set, stage, src, nullptr, sizeof(T), extent, false, false, nullptr, 0}; }
+template <class T> Staged staged_out(StageSet set, int stage, T* dst, size_t extent) { return {set, stage, nullptr, dst, sizeof(T), extent, false, false, nullptr, 0}; }
+template <class T> Staged staged_io(StageSet set, int stage, T* both, size_t extent) { return {set, stage, both, both, sizeof(T), extent, false, false, nullptr, 0}; }
+Staged staged_shared(StageSet set, int stage, const double* src, size_t extent) { return {set, stage, src, nullptr, 8, extent, true, false, nullptr, 0}; }
+Staged staged_device(StageSet set, int stage, bool on, size_t extent) { return {set, stage, nullptr, nullptr, 8, extent, false, on, nullptr, 0}; }
 
-// every stage of a host form grown, then its inputs on their way to the device
-int stage_in(ilqr_handle* h, std::initializer_list<Staged> arrays) {
-    for (const Staged& a : arrays) ILQR_TRY(grow(h, *a.st, a.bytes));
+ilqr_handle::Stage& stage_of(ilqr_handle* h, const Staged& a) {
+    switch (a.set) {
+        case IN_POL: return h->pol[a.stage];
+        case IN_CAND: return h->cand[a.stage];
+        case IN_SHIFT: return h->shift[a.stage];
+        case IN_SAMP: return h->samp[a.stage];
+        default: return h->plant[a.stage];
+    }
+}
+
+// A host form on ONE handle, whose instances are [lo, lo + B) of the caller's batch: every stage grown, then the inputs on their
+// way to the device, then launch(h, lo, arrays) with the device pointers, then the outputs on their way back and the stream
+// finished — the one synchronise, after which the caller may read them, and reuse the host arrays of the inputs.
+template <class F> int run_staged_on(ilqr_handle* h, size_t lo, std::vector<Staged> arrays, F& launch) {
+    HIP_TRY(hipSetDevice(h->device));
+    for (Staged& a : arrays) {
+        a.bytes = (a.src || a.dst || a.keep) ? (a.shared ? 1 : (size_t)h->B) * a.extent * a.elem : 0;
+        if (a.set == IN_RESIDENT) {
+            ILQR_TRY(resident_inputs(h));
+            a.p = a.stage == 0 ? h->d_x1 : h->d_u;
+        } else {
+            ILQR_TRY(grow(h, stage_of(h, a), a.bytes));
+            a.p = stage_of(h, a).p;
+        }
+        if (!a.bytes) a.p = nullptr;
+    }
     for (const Staged& a : arrays)
-        if (a.src && a.bytes) HIP_TRY(hipMemcpyAsync(a.st->p, a.src, a.bytes, hipMemcpyHostToDevice, h->stream));
+        if (a.src && a.bytes) HIP_TRY(hipMemcpyAsync(a.p, a.src, a.bytes, hipMemcpyHostToDevice, h->stream));
+    ILQR_TRY(launch(h, lo, arrays.data()));
+    for (const Staged& a : arrays)
+        if (a.dst && a.bytes) HIP_TRY(hipMemcpyAsync(a.dst, a.p, a.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
     return ILQR_OK;
 }
 
-// its outputs on their way back, and the stream finished: the caller may read them, and reuse the host arrays of the inputs
-int stage_out(ilqr_handle* h, std::initializer_list<Staged> arrays) {
-    for (const Staged& a : arrays)
-        if (a.dst && a.bytes) HIP_TRY(hipMemcpyAsync(a.dst, a.st->p, a.bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return ILQR_OK;
+// The same on any handle. A sharded one: one host thread per shard, which sees every per-instance array from its first instance
+// on (lo · extent elements further); shared arrays stay as they are, null stays null.
+template <class F> int run_staged(ilqr_handle* h, const std::vector<Staged>& arrays, F launch) {
+    if (!SHARDED(h)) return run_staged_on(h, 0, arrays, launch);
+    return each_shard(h, [&](ilqr_handle* s, size_t lo) {
+        std::vector<Staged> mine = arrays;
+        for (Staged& a : mine) {
+            if (a.shared) continue;
+            a.src = at((const char*)a.src, lo * a.extent * a.elem);
+            a.dst = at((char*)a.dst, lo * a.extent * a.elem);
+        }
+        return run_staged_on(s, lo, std::move(mine), launch); }, true);
 }
 
 // test hook (ilqr_device_math): the scalar routines of ilqr_math.hpp as the device executes them
@@ -1103,24 +1146,11 @@ int ilqr_rollout_policy(ilqr_handle* h, int32_t samples, double step_size, const
                         double* max_violation, int32_t* first_nonfinite, double* x, double* u) {
     ILQR_TRY(policy_check(h, samples, x1, w, cost, "ilqr_rollout_policy"));
     const size_t S = (size_t)samples, T = (size_t)h->L.T, N = T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        const size_t o = lo * S;
-        return ilqr_rollout_policy(s, samples, step_size, x1 + o * n, at(w, o * T * nwu), cost + o, at(max_violation, o), at(first_nonfinite, o),
-                                   at(x, o * T * n), at(u, o * N * m)); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t BS = (size_t)h->B * S;
-    const Staged s_x1 = staged_in(h->pol[POL_X1], x1, BS * n * 8);
-    const Staged s_w = staged_in(h->pol[POL_W], w, BS * T * nwu * 8);
-    const Staged s_cost = staged_out(h->pol[POL_COST], cost, BS * 8);
-    const Staged s_viol = staged_out(h->pol[POL_VIOL], max_violation, BS * 8);
-    const Staged s_nonfinite = staged_out(h->pol[POL_NONFINITE], first_nonfinite, BS * 4);
-    const Staged s_x = staged_out(h->pol[POL_X], x, BS * T * n * 8);
-    const Staged s_u = staged_out(h->pol[POL_U], u, BS * N * m * 8);
-    const auto arrays = {s_x1, s_w, s_cost, s_viol, s_nonfinite, s_x, s_u};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(policy_launch(h, samples, step_size, s_x1.dev<const double>(), s_w.dev<const double>(), s_cost.dev<double>(), s_viol.dev<double>(),
-                           s_nonfinite.dev<int32_t>(), s_x.dev<double>(), s_u.dev<double>()));
-    return stage_out(h, arrays);
+    return run_staged(h, {staged_in(IN_POL, POL_X1, x1, S * n), staged_in(IN_POL, POL_W, w, S * T * nwu), staged_out(IN_POL, POL_COST, cost, S),
+                          staged_out(IN_POL, POL_VIOL, max_violation, S), staged_out(IN_POL, POL_NONFINITE, first_nonfinite, S),
+                          staged_out(IN_POL, POL_X, x, S * T * n), staged_out(IN_POL, POL_U, u, S * N * m)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) {
+                          return policy_launch(s, samples, step_size, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].i(), a[5].d(), a[6].d()); });
 }
 
 // ---- scoring and selection of candidate initial guesses (ilqr_device_candidates.hpp), then the existing init_rollout on the winners
@@ -1165,25 +1195,12 @@ int ilqr_initialize_rollout_candidates(ilqr_handle* h, int32_t candidates, doubl
                                        int32_t* chosen, double* cost, double* max_violation, int32_t* first_nonfinite) {
     ILQR_TRY(candidates_check(h, candidates, violation_weight, x1, u, "ilqr_initialize_rollout_candidates"));
     const size_t S = (size_t)candidates, N = (size_t)h->L.T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        const size_t o = lo * S;
-        return ilqr_initialize_rollout_candidates(s, candidates, violation_weight, x1 + lo * n, u + o * N * m, at(chosen, lo), at(cost, o),
-                                                  at(max_violation, o), at(first_nonfinite, o)); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    ILQR_TRY(resident_inputs(h));
-    const size_t B = (size_t)h->B, BS = B * S;
-    ilqr_handle::Stage resident_x1{h->d_x1, B * n * 8};     // x1 goes straight into the resident input: a stage that never grows
-    const Staged s_x1 = staged_in(resident_x1, x1, B * n * 8);
-    const Staged s_u = staged_in(h->cand[CAND_U], u, BS * N * m * 8);        // (N == 0: no actions to stage; the launch gets d_u instead)
-    const Staged s_cost = staged_out(h->cand[CAND_COST], cost, BS * 8);
-    const Staged s_viol = staged_out(h->cand[CAND_VIOL], max_violation, BS * 8);
-    const Staged s_nonfinite = staged_out(h->cand[CAND_NONFINITE], first_nonfinite, BS * 4);
-    const Staged s_chosen = staged_out(h->cand[CAND_CHOSEN], chosen, B * 4);
-    const auto arrays = {s_x1, s_u, s_cost, s_viol, s_nonfinite, s_chosen};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(candidates_launch(h, candidates, violation_weight, h->d_x1, s_u.bytes ? s_u.dev<const double>() : h->d_u, s_chosen.dev<int32_t>(),
-                               s_cost.dev<double>(), s_viol.dev<double>(), s_nonfinite.dev<int32_t>()));
-    return stage_out(h, arrays);
+    // x1 goes straight into the resident input (N == 0: no actions to stage; the launch gets d_u instead)
+    return run_staged(h, {staged_in(IN_RESIDENT, 0, x1, n), staged_in(IN_CAND, CAND_U, u, S * N * m), staged_out(IN_CAND, CAND_COST, cost, S),
+                          staged_out(IN_CAND, CAND_VIOL, max_violation, S), staged_out(IN_CAND, CAND_NONFINITE, first_nonfinite, S),
+                          staged_out(IN_CAND, CAND_CHOSEN, chosen, 1)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) {
+                          return candidates_launch(s, candidates, violation_weight, s->d_x1, a[1].p ? a[1].d() : s->d_u, a[5].i(), a[2].d(), a[3].d(), a[4].i()); });
 }
 
 // ---- candidates drawn on the device around a base sequence (ilqr_device_sample.hpp), then the existing init_rollout on what was installed
@@ -1223,7 +1240,8 @@ static int sample_launch(ilqr_handle* h, int32_t candidates, int32_t mode, uint6
     ILQR_TRY(own_if_null(h, chosen, h->cand[CAND_CHOSEN], (size_t)h->B * 4));
     if (mode == ILQR_SAMPLE_BLEND) ILQR_TRY(own_if_null(h, weights, h->samp[SAMP_WEIGHTS], BS * 8));
     h->sample_sigma.assign(sigma, sigma + nu);        // the caller's array may go away before the (asynchronous) copy has read it
-    ILQR_TRY(stage_in(h, {staged_in(h->samp[SAMP_SIGMA], h->sample_sigma.data(), nu * 8)}));
+    ILQR_TRY(grow(h, h->samp[SAMP_SIGMA], nu * 8));
+    HIP_TRY(hipMemcpyAsync(h->samp[SAMP_SIGMA].p, h->sample_sigma.data(), nu * 8, hipMemcpyHostToDevice, h->stream));
     ilqr::SampleArgs a;
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.S = candidates; a.constrained = h->constrained;
     a.waves = waves_for(candidates);
@@ -1250,28 +1268,14 @@ int ilqr_sample_rollout_candidates(ilqr_handle* h, int32_t candidates, int32_t m
                                    double* cost, double* max_violation, int32_t* first_nonfinite, double* weights, double* u_out) {
     ILQR_TRY(sample_check(h, candidates, mode, first_instance, sigma, violation_weight, temperature, x1, base_u, "ilqr_sample_rollout_candidates"));
     const size_t S = (size_t)candidates, N = (size_t)h->L.T - 1, n = (size_t)h->L.nx, m = (size_t)h->L.nu;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        const size_t o = lo * S;
-        return ilqr_sample_rollout_candidates(s, candidates, mode, seed, first_instance + (int64_t)lo, sigma, violation_weight, temperature,
-                                              at(x1, lo * n), at(base_u, lo * N * m), at(chosen, lo), at(cost, o), at(max_violation, o),
-                                              at(first_nonfinite, o), at(weights, o), at(u_out, o * N * m)); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    ILQR_TRY(resident_inputs(h));
-    const size_t B = (size_t)h->B, BS = B * S;
-    const Staged s_cost = staged_out(h->cand[CAND_COST], cost, BS * 8);
-    const Staged s_viol = staged_out(h->cand[CAND_VIOL], max_violation, BS * 8);
-    const Staged s_nonfinite = staged_out(h->cand[CAND_NONFINITE], first_nonfinite, BS * 4);
-    const Staged s_chosen = staged_out(h->cand[CAND_CHOSEN], chosen, B * 4);
-    const Staged s_weights = staged_out(h->samp[SAMP_WEIGHTS], weights, BS * 8);
-    const Staged s_u_out = staged_out(h->samp[SAMP_U_OUT], u_out, BS * N * m * 8);
-    const auto arrays = {s_cost, s_viol, s_nonfinite, s_chosen, s_weights, s_u_out};
-    ILQR_TRY(stage_in(h, arrays));
     // the caller's x1 and base go straight into the resident inputs: the installation works in place
-    if (x1) HIP_TRY(hipMemcpyAsync(h->d_x1, x1, B * n * 8, hipMemcpyHostToDevice, h->stream));
-    if (base_u) HIP_TRY(hipMemcpyAsync(h->d_u, base_u, B * N * m * 8, hipMemcpyHostToDevice, h->stream));
-    ILQR_TRY(sample_launch(h, candidates, mode, seed, first_instance, sigma, violation_weight, temperature, h->d_x1, h->d_u, s_chosen.dev<int32_t>(),
-                           s_cost.dev<double>(), s_viol.dev<double>(), s_nonfinite.dev<int32_t>(), s_weights.dev<double>(), s_u_out.dev<double>()));
-    return stage_out(h, arrays);
+    return run_staged(h, {staged_in(IN_RESIDENT, 0, x1, n), staged_in(IN_RESIDENT, 1, base_u, N * m), staged_out(IN_CAND, CAND_COST, cost, S),
+                          staged_out(IN_CAND, CAND_VIOL, max_violation, S), staged_out(IN_CAND, CAND_NONFINITE, first_nonfinite, S),
+                          staged_out(IN_CAND, CAND_CHOSEN, chosen, 1), staged_out(IN_SAMP, SAMP_WEIGHTS, weights, S),
+                          staged_out(IN_SAMP, SAMP_U_OUT, u_out, S * N * m)},
+                      [&](ilqr_handle* s, size_t lo, const Staged* a) {
+                          return sample_launch(s, candidates, mode, seed, first_instance + (int64_t)lo, sigma, violation_weight, temperature, s->d_x1,
+                                               s->d_u, a[5].i(), a[2].d(), a[3].d(), a[4].i(), a[6].d(), a[7].d()); });
 }
 
 // ---- receding-horizon shift (ilqr_device_shift.hpp), then the existing init_rollout on the shifted inputs
@@ -1294,7 +1298,7 @@ static int shift_check(const ilqr_handle* h, int32_t steps, int32_t tail, int32_
 // x1, w_tail: null or device pointers on h's device. w_tail_ld < 0: the rows of ONE call, [B][steps][nw]; else instance b's rows
 // start at row b · w_tail_ld + w_tail_row0 (the loop's run-long array)
 static int shift_launch(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail,
-                        long long w_tail_ld = -1, long long w_tail_row0 = 0) {
+                        long long w_tail_ld, long long w_tail_row0) {
     if (!h->vt->launch_shift) return fail(ILQR_ERR_MODEL, "this model module has no horizon shift kernel");
     ILQR_TRY(resident_inputs(h));
     ilqr::ShiftArgs a;
@@ -1313,21 +1317,15 @@ int ilqr_shift_horizon_device(ilqr_handle* h, int32_t steps, int32_t tail, int32
     ILQR_TRY(shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon_device"));
     if (SHARDED(h)) return refuse_sharded("ilqr_shift_horizon");
     HIP_TRY(hipSetDevice(h->device));
-    return shift_launch(h, steps, tail, feedback, x1, w_tail);
+    return shift_launch(h, steps, tail, feedback, x1, w_tail, -1, 0);
 }
 
 int ilqr_shift_horizon(ilqr_handle* h, int32_t steps, int32_t tail, int32_t feedback, const double* x1, const double* w_tail) {
     ILQR_TRY(shift_check(h, steps, tail, feedback, w_tail, "ilqr_shift_horizon"));
     const size_t n = (size_t)h->L.nx, kw = (size_t)steps * (size_t)(h->L.nw - h->n_sel);
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_shift_horizon(s, steps, tail, feedback, at(x1, lo * n), at(w_tail, lo * kw)); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const Staged s_x1 = staged_in(h->shift[SHIFT_X1], x1, (size_t)h->B * n * 8);
-    const Staged s_w_tail = staged_in(h->shift[SHIFT_W_TAIL], w_tail, (size_t)h->B * kw * 8);
-    const auto arrays = {s_x1, s_w_tail};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(shift_launch(h, steps, tail, feedback, s_x1.dev<const double>(), s_w_tail.dev<const double>()));
-    return stage_out(h, arrays);               // (inputs only: the synchronise, after which the caller may reuse its host arrays)
+    // (inputs only: what comes back is the synchronise, after which the caller may reuse its host arrays)
+    return run_staged(h, {staged_in(IN_SHIFT, SHIFT_X1, x1, n), staged_in(IN_SHIFT, SHIFT_W_TAIL, w_tail, kw)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) { return shift_launch(s, steps, tail, feedback, a[0].d(), a[1].d(), -1, 0); });
 }
 
 // ---- receding-horizon shift of the duals and penalties (ilqr_device_duals.hpp)
@@ -1404,7 +1402,7 @@ static int plant_check(const ilqr_handle* h, int32_t steps, int32_t feedback, in
 
 // what a plant launch takes of the handle and of the call; the arrays are the caller's to fill in
 static ilqr::PlantArgs plant_args(const ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
-                                  const double* sigma_x, const double* u_min = nullptr, const double* u_max = nullptr) {
+                                  const double* sigma_x, const double* u_min, const double* u_max) {
     ilqr::PlantArgs a = {};
     a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.feedback = feedback ? 1 : 0; a.n_sel = h->n_sel; a.step0 = step0;
     a.noise = sigma_x != nullptr; a.nf_global = 0; a.seed = seed; a.b0 = first_instance;
@@ -1459,22 +1457,13 @@ static int plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t 
     if (!x) return fail(ILQR_ERR_INVALID, std::string(who) + ": null x");
     ILQR_TRY(plant_check(h, steps, feedback, first_instance, step0, steps, sigma_x, u_min, u_max, w_plant, who));
     const size_t k = (size_t)steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return plant_step(s, steps, feedback, seed, first_instance + (int64_t)lo, step0, sigma_x, u_min, u_max, at(w_plant, lo * k * nwu), x + lo * n,
-                          at(x_out, lo * (k + 1) * n), at(u_out, lo * k * m), at(first_nonfinite, lo), at(saturated, lo), who); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    const Staged s_x = {&h->plant[PLANT_X], x, x, B * n * 8};                // the plant state goes in and comes back
-    const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * k * nwu * 8);
-    const Staged s_x_out = staged_out(h->plant[PLANT_X_OUT], x_out, B * (k + 1) * n * 8);
-    const Staged s_u_out = staged_out(h->plant[PLANT_U_OUT], u_out, B * k * m * 8);
-    const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
-    const Staged s_saturated = staged_out(h->plant[PLANT_SATURATED], saturated, B * 4);
-    const auto arrays = {s_x, s_w, s_x_out, s_u_out, s_nonfinite, s_saturated};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(plant_launch(h, plant_args(h, steps, feedback, seed, first_instance, step0, sigma_x, u_min, u_max), s_w.dev<const double>(),
-                          s_x.dev<double>(), s_x_out.dev<double>(), s_u_out.dev<double>(), s_nonfinite.dev<int32_t>(), s_saturated.dev<int32_t>()));
-    return stage_out(h, arrays);
+    // the plant state goes in and comes back
+    return run_staged(h, {staged_io(IN_PLANT, PLANT_X, x, n), staged_in(IN_PLANT, PLANT_W, w_plant, k * nwu), staged_out(IN_PLANT, PLANT_X_OUT, x_out, (k + 1) * n),
+                          staged_out(IN_PLANT, PLANT_U_OUT, u_out, k * m), staged_out(IN_PLANT, PLANT_NONFINITE, first_nonfinite, 1),
+                          staged_out(IN_PLANT, PLANT_SATURATED, saturated, 1)},
+                      [&](ilqr_handle* s, size_t lo, const Staged* a) {
+                          return plant_launch(s, plant_args(s, steps, feedback, seed, first_instance + (int64_t)lo, step0, sigma_x, u_min, u_max), a[1].d(),
+                                              a[0].d(), a[2].d(), a[3].d(), a[4].i(), a[5].i()); });
 }
 
 int ilqr_plant_step(ilqr_handle* h, int32_t steps, int32_t feedback, uint64_t seed, int64_t first_instance, int32_t step0,
@@ -1526,15 +1515,8 @@ int ilqr_plant_measure(ilqr_handle* h, uint64_t seed, int64_t first_instance, in
     if (!x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure: null x or y");
     ILQR_TRY(measure_check(h, first_instance, step, sigma_y, "ilqr_plant_measure"));
     const size_t n = (size_t)h->L.nx;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_plant_measure(s, seed, first_instance + (int64_t)lo, step, sigma_y, x + lo * n, y + lo * n); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const Staged s_x = staged_in(h->plant[PLANT_X], x, (size_t)h->B * n * 8);
-    const Staged s_y = staged_out(h->plant[PLANT_Y], y, (size_t)h->B * n * 8);
-    const auto arrays = {s_x, s_y};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(measure_launch(h, seed, first_instance, step, sigma_y, s_x.dev<const double>(), s_y.dev<double>()));
-    return stage_out(h, arrays);
+    return run_staged(h, {staged_in(IN_PLANT, PLANT_X, x, n), staged_out(IN_PLANT, PLANT_Y, y, n)}, [&](ilqr_handle* s, size_t lo, const Staged* a) {
+        return measure_launch(s, seed, first_instance + (int64_t)lo, step, sigma_y, a[0].d(), a[1].d()); });
 }
 
 // ---- the realised stage cost and violation of plant steps (ilqr_device_score.hpp)
@@ -1580,19 +1562,9 @@ int ilqr_plant_score_device(ilqr_handle* h, int32_t steps, const double* w_plant
 int ilqr_plant_score(ilqr_handle* h, int32_t steps, const double* w_plant, const double* x, const double* u, double* cost, double* violation) {
     ILQR_TRY(score_check(h, steps, w_plant, x, u, cost, "ilqr_plant_score"));
     const size_t k = (size_t)steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_plant_score(s, steps, at(w_plant, lo * k * nwu), x + lo * (k + 1) * n, u + lo * k * m, cost + lo * k, at(violation, lo * k)); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * k * nwu * 8);
-    const Staged s_x = staged_in(h->plant[PLANT_X_OUT], x, B * (k + 1) * n * 8);
-    const Staged s_u = staged_in(h->plant[PLANT_U_OUT], u, B * k * m * 8);
-    const Staged s_cost = staged_out(h->plant[PLANT_COST], cost, B * k * 8);
-    const Staged s_viol = staged_out(h->plant[PLANT_VIOL], violation, B * k * 8);
-    const auto arrays = {s_w, s_x, s_u, s_cost, s_viol};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(score_launch(h, steps, s_w.dev<const double>(), s_x.dev<const double>(), s_u.dev<const double>(), s_cost.dev<double>(), s_viol.dev<double>()));
-    return stage_out(h, arrays);
+    return run_staged(h, {staged_in(IN_PLANT, PLANT_W, w_plant, k * nwu), staged_in(IN_PLANT, PLANT_X_OUT, x, (k + 1) * n), staged_in(IN_PLANT, PLANT_U_OUT, u, k * m),
+                          staged_out(IN_PLANT, PLANT_COST, cost, k), staged_out(IN_PLANT, PLANT_VIOL, violation, k)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) { return score_launch(s, steps, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].d()); });
 }
 
 // ---- the extended Kalman filter between sensor and controller (ilqr_device_estimate.hpp)
@@ -1668,16 +1640,9 @@ int ilqr_estimate_predict(ilqr_handle* h, int32_t steps, int32_t feedback, const
     if (!xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_predict: null xhat or P");
     ILQR_TRY(predict_check(h, steps, feedback, u_min, u_max, q, "ilqr_estimate_predict"));
     const size_t n = (size_t)h->L.nx;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_estimate_predict(s, steps, feedback, u_min, u_max, q, xhat + lo * n, P + lo * n * n); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    const Staged s_x = {&h->plant[PLANT_XC], xhat, xhat, B * n * 8};           // the estimate and its covariance go in and come back
-    const Staged s_P = {&h->plant[EST_P], P, P, B * n * n * 8};
-    const auto arrays = {s_x, s_P};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(predict_launch(h, steps, feedback, u_min, u_max, q, s_x.dev<double>(), s_P.dev<double>()));
-    return stage_out(h, arrays);
+    // the estimate and its covariance go in and come back
+    return run_staged(h, {staged_io(IN_PLANT, PLANT_XC, xhat, n), staged_io(IN_PLANT, EST_P, P, n * n)}, [&](ilqr_handle* s, size_t, const Staged* a) {
+        return predict_launch(s, steps, feedback, u_min, u_max, q, a[0].d(), a[1].d()); });
 }
 
 int ilqr_estimate_update_device(ilqr_handle* h, const int32_t* measured, const double* r, const double* y, double* xhat, double* P,
@@ -1694,22 +1659,10 @@ int ilqr_estimate_update(ilqr_handle* h, const int32_t* measured, const double* 
     if (!xhat || !P || !y) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update: null xhat, P or y");
     ILQR_TRY(update_check(h, measured, r, "ilqr_estimate_update"));
     const size_t n = (size_t)h->L.nx;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_estimate_update(s, measured, r, y + lo * n, xhat + lo * n, P + lo * n * n, at(innovation, lo * n), at(nis, lo), at(first_bad, lo)); },
-        true);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    const Staged s_y = staged_in(h->plant[EST_Y], y, B * n * 8);
-    const Staged s_x = {&h->plant[PLANT_XC], xhat, xhat, B * n * 8};
-    const Staged s_P = {&h->plant[EST_P], P, P, B * n * n * 8};
-    const Staged s_inn = staged_out(h->plant[EST_INNOVATION], innovation, B * n * 8);
-    const Staged s_nis = staged_out(h->plant[EST_NIS], nis, B * 8);
-    const Staged s_bad = staged_out(h->plant[EST_FIRST_BAD], first_bad, B * 4);
-    const auto arrays = {s_y, s_x, s_P, s_inn, s_nis, s_bad};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(update_launch(h, measured, r, s_y.dev<const double>(), s_x.dev<double>(), s_P.dev<double>(), s_inn.dev<double>(), s_nis.dev<double>(),
-                           s_bad.dev<int32_t>()));
-    return stage_out(h, arrays);
+    return run_staged(h, {staged_in(IN_PLANT, EST_Y, y, n), staged_io(IN_PLANT, PLANT_XC, xhat, n), staged_io(IN_PLANT, EST_P, P, n * n),
+                          staged_out(IN_PLANT, EST_INNOVATION, innovation, n), staged_out(IN_PLANT, EST_NIS, nis, 1), staged_out(IN_PLANT, EST_FIRST_BAD, first_bad, 1)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) {
+                          return update_launch(s, measured, r, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].i()); });
 }
 
 // ---- a linear sensor y = H x + v with ny outputs (ilqr_device_sensor.hpp)
@@ -1777,26 +1730,13 @@ int ilqr_estimate_update_linear(ilqr_handle* h, int32_t ny, int32_t per_instance
     if (!H || !r || !y || !xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update_linear: null H, r, y, xhat or P");
     ILQR_TRY(sensor_check(h, ny, per_instance_H, H, r, nullptr, "ilqr_estimate_update_linear"));
     const size_t n = (size_t)h->L.nx, m = (size_t)ny;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_estimate_update_linear(s, ny, per_instance_H, per_instance_H ? H + lo * m * n : H, r, y + lo * m, at(yhat, lo * m), xhat + lo * n,
-                                           P + lo * n * n, at(innovation, lo * m), at(nis, lo), at(first_bad, lo)); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    const Staged s_H = staged_in(h->plant[SENS_H], H, (per_instance_H ? B : 1) * m * n * 8);
-    const Staged s_r = staged_in(h->plant[SENS_R], r, m * 8);
-    const Staged s_y = staged_in(h->plant[EST_Y], y, B * m * 8);
-    const Staged s_yhat = staged_in(h->plant[SENS_YHAT], yhat, B * m * 8);
-    const Staged s_x = {&h->plant[PLANT_XC], xhat, xhat, B * n * 8};           // the estimate and its covariance go in and come back
-    const Staged s_P = {&h->plant[EST_P], P, P, B * n * n * 8};
-    const Staged s_inn = staged_out(h->plant[EST_INNOVATION], innovation, B * m * 8);
-    const Staged s_nis = staged_out(h->plant[EST_NIS], nis, B * 8);
-    const Staged s_bad = staged_out(h->plant[EST_FIRST_BAD], first_bad, B * 4);
-    const auto arrays = {s_H, s_r, s_y, s_yhat, s_x, s_P, s_inn, s_nis, s_bad};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(sensor_update_launch(h, ny, per_instance_H, s_H.dev<const double>(), s_r.dev<const double>(), s_y.dev<const double>(),
-                                  s_yhat.dev<const double>(), s_x.dev<double>(), s_P.dev<double>(), s_inn.dev<double>(), s_nis.dev<double>(),
-                                  s_bad.dev<int32_t>()));
-    return stage_out(h, arrays);
+    // the estimate and its covariance go in and come back
+    return run_staged(h, {per_instance_H ? staged_in(IN_PLANT, SENS_H, H, m * n) : staged_shared(IN_PLANT, SENS_H, H, m * n), staged_shared(IN_PLANT, SENS_R, r, m),
+                          staged_in(IN_PLANT, EST_Y, y, m), staged_in(IN_PLANT, SENS_YHAT, yhat, m), staged_io(IN_PLANT, PLANT_XC, xhat, n),
+                          staged_io(IN_PLANT, EST_P, P, n * n), staged_out(IN_PLANT, EST_INNOVATION, innovation, m), staged_out(IN_PLANT, EST_NIS, nis, 1),
+                          staged_out(IN_PLANT, EST_FIRST_BAD, first_bad, 1)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) {
+                          return sensor_update_launch(s, ny, per_instance_H, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].d(), a[6].d(), a[7].d(), a[8].i()); });
 }
 
 int ilqr_plant_measure_linear_device(ilqr_handle* h, uint64_t seed, int64_t first_instance, int32_t step, int32_t ny, const double* H,
@@ -1820,38 +1760,38 @@ int ilqr_plant_measure_linear(ilqr_handle* h, uint64_t seed, int64_t first_insta
     ILQR_TRY(measure_check(h, first_instance, step, nullptr, "ilqr_plant_measure_linear"));
     ILQR_TRY(sensor_check(h, ny, 0, H, nullptr, sigma_y, "ilqr_plant_measure_linear"));
     const size_t n = (size_t)h->L.nx, m = (size_t)ny;
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        return ilqr_plant_measure_linear(s, seed, first_instance + (int64_t)lo, step, ny, H, sigma_y, x + lo * n, y + lo * m); }, true);
-    HIP_TRY(hipSetDevice(h->device));
-    const Staged s_H = staged_in(h->plant[SENS_H], H, m * n * 8);
-    const Staged s_sigma = staged_in(h->plant[SENS_SIGMA], sigma_y, m * 8);
-    const Staged s_x = staged_in(h->plant[PLANT_X], x, (size_t)h->B * n * 8);
-    const Staged s_y = staged_out(h->plant[PLANT_Y], y, (size_t)h->B * m * 8);
-    const auto arrays = {s_H, s_sigma, s_x, s_y};
-    ILQR_TRY(stage_in(h, arrays));
-    ILQR_TRY(measure_linear_launch(h, seed, first_instance, step, ny, s_H.dev<const double>(), s_sigma.dev<const double>(), s_x.dev<const double>(),
-                                   s_y.dev<double>()));
-    return stage_out(h, arrays);
+    return run_staged(h, {staged_shared(IN_PLANT, SENS_H, H, m * n), staged_shared(IN_PLANT, SENS_SIGMA, sigma_y, m), staged_in(IN_PLANT, PLANT_X, x, n),
+                          staged_out(IN_PLANT, PLANT_Y, y, m)},
+                      [&](ilqr_handle* s, size_t lo, const Staged* a) {
+                          return measure_linear_launch(s, seed, first_instance + (int64_t)lo, step, ny, a[0].d(), a[1].d(), a[2].d(), a[3].d()); });
 }
 
 // ---- the closed MPC loop, enqueued once: per period plant step, score, horizon shift, dual shift, solve, log row
 static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
-// everything its constituents refuse for these arguments, before any launch
-// The seam between plant and controller is in use: limits, measurement noise, a delay, or one of the two outputs that report on it.
-// Otherwise the loop hands the shift the plant state itself: no launch, no buffer and no argument of it differs from ilqr_mpc_run's.
-static bool mpc_measured(const ilqr_plant_io* io, const double* y_cl, const int32_t* saturated, const ilqr_estimator* est = nullptr,
-                         const ilqr_sensor* sens = nullptr) {
-    return (io && (io->u_min || io->u_max || io->sigma_y || io->delay)) || y_cl || saturated || est || sens;
+// One run of the loop as an entry point hands it over: the descriptor, the seam (io), the filter (est: the extended Kalman filter, or
+// sens: the linear sensor in its place), every input and output array of the batch, and the entry point's name. What an entry point
+// does not offer stays null.
+struct MpcRun {
+    const ilqr_mpc_desc* d; const ilqr_plant_io* io; const ilqr_estimator* est; const ilqr_sensor* sens;
+    const double *x0, *xhat0, *w_plant, *w_preview;
+    double *Pcov, *x_cl, *u_cl, *log, *cl_cost, *cl_violation, *y_cl, *xhat_cl, *pdiag_cl, *nis_cl;
+    int32_t *first_nonfinite, *saturated;
+    const char* who;
+};
+// The seam between plant and controller is in use: limits, measurement noise, a delay, a filter, or one of the two outputs that report
+// on it. Otherwise the loop hands the shift the plant state itself: no launch, no buffer and no argument of it differs from ilqr_mpc_run's.
+static bool mpc_measured(const MpcRun& r) {
+    return (r.io && (r.io->u_min || r.io->u_max || r.io->sigma_y || r.io->delay)) || r.y_cl || r.saturated || r.est || r.sens;
 }
+// everything its constituents refuse for these arguments, before any launch
 // measured: the run goes through the measurement slot (mpc_measured)
-static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, bool measured, const double* w_plant,
-                     const double* w_preview, const double* cl_cost, const double* cl_violation, const ilqr_estimator* est, const double* xhat0,
-                     const double* Pcov, const double* xhat_cl, const double* pdiag_cl, const double* nis_cl, const ilqr_sensor* sens,
-                     const char* who) {
+static int mpc_check(const ilqr_handle* h, const MpcRun& r, bool measured) {
+    const ilqr_mpc_desc* d = r.d; const ilqr_plant_io* io = r.io; const ilqr_estimator* est = r.est; const ilqr_sensor* sens = r.sens;
+    const char* who = r.who;
     const std::string me(who);
     if (!d) return fail(ILQR_ERR_INVALID, me + ": null descriptor");
     if (sens) {                                    // the linear sensor in the estimator's place; what needs no handle, as its calls order it
-        if (!Pcov) return fail(ILQR_ERR_INVALID, me + ": a sensor with a null P");
+        if (!r.Pcov) return fail(ILQR_ERR_INVALID, me + ": a sensor with a null P");
         if (io && io->sigma_y) return fail(ILQR_ERR_INVALID, me + ": io->sigma_y together with a sensor: the sensor's own sigma_y [ny] replaces it");
         if (!sens->H || !sens->r) return fail(ILQR_ERR_INVALID, me + ": null H or r");
         if (sens->ny < 1 || sens->ny > ilqr::SENSOR_MAX_NY) return fail(ILQR_ERR_INVALID, me + ": ny must lie in 1 .. 64");
@@ -1860,14 +1800,14 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_pl
             if (!(sens->r[j] > 0.0) || !std::isfinite(sens->r[j])) return fail(ILQR_ERR_INVALID, me + ": r must be finite and > 0");
         ILQR_TRY(sigma_check(sens->sigma_y, sens->ny, me, "sigma_y"));
     }
-    if (!est && !sens && (xhat0 || Pcov || xhat_cl || pdiag_cl || nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
-    if (est && !Pcov) return fail(ILQR_ERR_INVALID, me + ": an estimator with a null P");
+    if (!est && !sens && (r.xhat0 || r.Pcov || r.xhat_cl || r.pdiag_cl || r.nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
+    if (est && !r.Pcov) return fail(ILQR_ERR_INVALID, me + ": an estimator with a null P");
     if (est) {                                     // what needs no handle, as the two estimator calls order it
         if (!est->r) return fail(ILQR_ERR_INVALID, me + ": null r");
         ILQR_TRY(variance_check(est->measured, est->q, est->r, 1, me));
     }
     if (d->periods < 1) return fail(ILQR_ERR_INVALID, me + ": periods must be >= 1");
-    if (cl_violation && !cl_cost) return fail(ILQR_ERR_INVALID, me + ": cl_violation without cl_cost: the two scores come from one launch");
+    if (r.cl_violation && !r.cl_cost) return fail(ILQR_ERR_INVALID, me + ": cl_violation without cl_cost: the two scores come from one launch");
     if (io && io->delay != 0 && io->delay != 1) return fail(ILQR_ERR_INVALID, me + ": delay must be 0 or 1");
     const int64_t run_steps = (int64_t)d->periods * (int64_t)(d->steps > 0 ? d->steps : 0);
     // the last measurement: of the state after the run's last plant step (delay 0), before its last period (delay 1)
@@ -1877,10 +1817,10 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_pl
         ILQR_TRY(sigma_check(io ? io->sigma_y : nullptr, 1, me, "sigma_y"));
     }
     ILQR_TRY(plant_check(h, d->steps, d->plant_feedback, d->first_instance, 0, run_steps, d->sigma_x, io ? io->u_min : nullptr,
-                         io ? io->u_max : nullptr, w_plant, who));
+                         io ? io->u_max : nullptr, r.w_plant, who));
     if (measured) ILQR_TRY(measure_check(h, d->first_instance, last_measured, io ? io->sigma_y : nullptr, who));
-    if (w_preview && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_preview given, but this model has no parameters (num_parameter == 0)");
-    ILQR_TRY(shift_check(h, d->steps, d->shift_tail, d->shift_feedback, w_preview, who));
+    if (r.w_preview && h->vt->nw - h->n_sel <= 0) return fail(ILQR_ERR_INVALID, me + ": w_preview given, but this model has no parameters (num_parameter == 0)");
+    ILQR_TRY(shift_check(h, d->steps, d->shift_tail, d->shift_feedback, r.w_preview, who));
     if (d->warm) {
         if (!h->constrained) return fail(ILQR_ERR_INVALID, me + ": warm on a handle created unconstrained: it has no duals to keep");
         ILQR_TRY(duals_check(h, d->steps, d->duals_tail, d->duals_penalty, who));
@@ -1893,180 +1833,234 @@ static int mpc_check(const ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_pl
     return ILQR_OK;
 }
 
-// ilqr_mpc_run is this with w_preview, cl_cost and cl_violation null and nothing measured (mpc_measured); ilqr_mpc_run_preview with
-// nothing measured: no launch, no buffer and no argument of it changes then; ilqr_mpc_run_io with est and what follows it null.
-// est: the filter stands between the measurement and the controller's state xc, which then IS the estimate x̂
-static int mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const double* x0, const double* w_plant, const double* w_preview,
-                   double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
-                   int32_t* saturated, const char* who, const ilqr_estimator* est = nullptr, const double* xhat0 = nullptr, double* Pcov = nullptr,
-                   double* xhat_cl = nullptr, double* pdiag_cl = nullptr, double* nis_cl = nullptr, const ilqr_sensor* sens = nullptr) {
-    const bool measured = mpc_measured(io, y_cl, saturated, est, sens);
-    ILQR_TRY(mpc_check(h, d, io, measured, w_plant, w_preview, cl_cost, cl_violation, est, xhat0, Pcov, xhat_cl, pdiag_cl, nis_cl, sens, who));
-    const bool filt = est || sens;                 // a filter stands between the measurement and the controller
-    const double* fq = est ? est->q : sens ? sens->q : nullptr;
-    const size_t ym_n = sens ? (size_t)sens->ny : (size_t)h->L.nx;           // the numbers of one measurement
-    const size_t P = (size_t)d->periods, k = (size_t)d->steps, R = P * k, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
-    if (SHARDED(h)) return each_shard(h, [&](ilqr_handle* s, size_t lo) {
-        ilqr_mpc_desc sd = *d;
-        sd.first_instance += (int64_t)lo;
-        return mpc_run(s, &sd, io, at(x0, lo * n), at(w_plant, lo * R * nwu), at(w_preview, lo * R * nwu), at(x_cl, lo * (R + 1) * n), at(u_cl, lo * R * m),
-                       at(log, lo * P * ILQR_MPC_LOG_W), at(first_nonfinite, lo), at(cl_cost, lo * R), at(cl_violation, lo * R), at(y_cl, lo * P * ym_n),
-                       at(saturated, lo), who, est, at(xhat0, lo * n), at(Pcov, lo * n * n), at(xhat_cl, lo * P * n), at(pdiag_cl, lo * P * n),
-                       at(nis_cl, lo * P), sens); }, true);
-    if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
-    const bool score = cl_cost != nullptr;
-    if (score && !h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
-    if (measured && !h->vt->launch_plant_measure) return fail(ILQR_ERR_MODEL, "this model module has no measurement kernel");
-    if (est && (!h->vt->launch_estimate_predict || !h->vt->launch_estimate_update)) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
-    if (sens && (!h->vt->launch_estimate_predict || !h->vt->launch_sensor_update || !h->vt->launch_plant_measure_linear))
-        return fail(ILQR_ERR_MODEL, "this model module has no linear sensor kernel");
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t B = (size_t)h->B;
-    const Staged s_x = staged_in(h->plant[PLANT_X], x0, B * n * 8);
-    const Staged s_w = staged_in(h->plant[PLANT_W], w_plant, B * R * nwu * 8);
-    const Staged s_preview = staged_in(h->plant[PLANT_W_PREVIEW], w_preview, B * R * nwu * 8);
-    const Staged s_x_cl = staged_out(h->plant[PLANT_X_OUT], x_cl, B * (R + 1) * n * 8);
-    const Staged s_u_cl = staged_out(h->plant[PLANT_U_OUT], u_cl, B * R * m * 8);
-    const Staged s_log = staged_out(h->plant[PLANT_LOG], log, B * P * ILQR_MPC_LOG_W * 8);
-    const Staged s_nonfinite = staged_out(h->plant[PLANT_NONFINITE], first_nonfinite, B * 4);
-    const Staged s_cost = staged_out(h->plant[PLANT_COST], cl_cost, B * R * 8);
-    const Staged s_viol = staged_out(h->plant[PLANT_VIOL], cl_violation, B * R * 8);
-    const Staged s_y_cl = staged_out(h->plant[PLANT_Y], y_cl, B * P * ym_n * 8);
-    const Staged s_saturated = staged_out(h->plant[PLANT_SATURATED], saturated, B * 4);
-    const Staged s_xhat0 = staged_in(h->plant[PLANT_XC], xhat0, B * n * 8);
-    const Staged s_P = {&h->plant[EST_P], Pcov, Pcov, Pcov ? B * n * n * 8 : 0};          // P0 goes in, the last covariance comes back
-    const Staged s_xhat_cl = staged_out(h->plant[EST_XHAT_CL], xhat_cl, B * P * n * 8);
-    const Staged s_pdiag_cl = staged_out(h->plant[EST_PDIAG_CL], pdiag_cl, B * P * n * 8);
-    const Staged s_nis_cl = staged_out(h->plant[EST_NIS_CL], nis_cl, B * P * 8);
-    // the sensor's H, r and sigma_y: copied once, before the first launch (the call synchronises before it returns)
-    const Staged s_sens_H = staged_in(h->plant[SENS_H], sens ? sens->H : nullptr, ym_n * n * 8);
-    const Staged s_sens_r = staged_in(h->plant[SENS_R], sens ? sens->r : nullptr, ym_n * 8);
-    const Staged s_sens_sigma = staged_in(h->plant[SENS_SIGMA], sens ? sens->sigma_y : nullptr, ym_n * 8);
-    const auto arrays = {s_x, s_w, s_preview, s_x_cl, s_u_cl, s_log, s_nonfinite, s_cost, s_viol, s_y_cl, s_saturated, s_xhat0, s_P, s_xhat_cl, s_pdiag_cl,
-                         s_nis_cl, s_sens_H, s_sens_r, s_sens_sigma};
-    // Every buffer of the run exists before its first launch — the plant state also without an x0, what the shift would allocate
-    // in its first call, the closed-loop trajectory the score reads even when the caller does not ask for it, and the controller's
-    // state of a measured run — so that nothing between the first plant launch and the synchronise at the end waits for the device.
-    ILQR_TRY(grow(h, h->plant[PLANT_X], B * n * 8));
-    ILQR_TRY(resident_inputs(h));
-    if (h->L.nw > 0) ILQR_TRY(grow(h, h->shift[SHIFT_W_STAGE], B * (size_t)h->L.T * (size_t)h->L.nw * 8));
-    if (score) {
-        ILQR_TRY(grow(h, h->plant[PLANT_X_OUT], B * (R + 1) * n * 8));
-        ILQR_TRY(grow(h, h->plant[PLANT_U_OUT], B * R * m * 8));
+// the arrays of a run (mpc_arrays) by name
+enum { M_X, M_W, M_PREVIEW, M_X_CL, M_U_CL, M_LOG, M_NONFINITE, M_COST, M_VIOL, M_Y_CL, M_SATURATED, M_XC, M_P, M_XHAT_CL, M_PDIAG_CL, M_NIS_CL, M_SENS_H,
+       M_SENS_R, M_SENS_SIGMA, M_YM, M_NIS, M_W_STAGE, M_RESIDENT };
+
+// Every buffer of the run exists before its first launch — the plant state also without an x0, the closed-loop trajectory the score
+// reads even when the caller does not ask for it, the controller's state of a measured run, the period's measurement and nis of a
+// filter, what the shift would allocate in its first call and the resident inputs — so that nothing between the first plant launch
+// and the synchronise at the end waits for the device. The sensor's H, r and sigma_y are copied once, before the first launch.
+static std::vector<Staged> mpc_arrays(const ilqr_handle* h, const MpcRun& r, bool measured) {
+    const bool filt = r.est || r.sens, score = r.cl_cost != nullptr;
+    const size_t ym_n = r.sens ? (size_t)r.sens->ny : (size_t)h->L.nx;       // the numbers of one measurement
+    const size_t P = (size_t)r.d->periods, R = P * (size_t)r.d->steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
+    return {staged_in(IN_PLANT, PLANT_X, r.x0, n).kept(true), staged_in(IN_PLANT, PLANT_W, r.w_plant, R * nwu), staged_in(IN_PLANT, PLANT_W_PREVIEW, r.w_preview, R * nwu),
+            staged_out(IN_PLANT, PLANT_X_OUT, r.x_cl, (R + 1) * n).kept(score), staged_out(IN_PLANT, PLANT_U_OUT, r.u_cl, R * m).kept(score),
+            staged_out(IN_PLANT, PLANT_LOG, r.log, P * ILQR_MPC_LOG_W), staged_out(IN_PLANT, PLANT_NONFINITE, r.first_nonfinite, 1),
+            staged_out(IN_PLANT, PLANT_COST, r.cl_cost, R), staged_out(IN_PLANT, PLANT_VIOL, r.cl_violation, R),
+            staged_out(IN_PLANT, PLANT_Y, r.y_cl, P * ym_n), staged_out(IN_PLANT, PLANT_SATURATED, r.saturated, 1),
+            staged_in(IN_PLANT, PLANT_XC, r.xhat0, n).kept(measured), staged_io(IN_PLANT, EST_P, r.Pcov, n * n),      // P0 in, the last covariance back
+            staged_out(IN_PLANT, EST_XHAT_CL, r.xhat_cl, P * n), staged_out(IN_PLANT, EST_PDIAG_CL, r.pdiag_cl, P * n), staged_out(IN_PLANT, EST_NIS_CL, r.nis_cl, P),
+            staged_shared(IN_PLANT, SENS_H, r.sens ? r.sens->H : nullptr, ym_n * n), staged_shared(IN_PLANT, SENS_R, r.sens ? r.sens->r : nullptr, ym_n),
+            staged_shared(IN_PLANT, SENS_SIGMA, r.sens ? r.sens->sigma_y : nullptr, ym_n),
+            staged_device(IN_PLANT, EST_Y, filt, ym_n), staged_device(IN_PLANT, EST_NIS, filt, 1),
+            staged_device(IN_SHIFT, SHIFT_W_STAGE, h->L.nw > 0, (size_t)h->L.T * (size_t)h->L.nw), staged_device(IN_RESIDENT, 0, true, n)};
+}
+
+// A run on one handle while it is enqueued: its arrays on the device, the plant state xp, the controller's view of it xc (what the shift
+// is handed; with a filter the estimate x̂), where the measurement lands (ym: with a filter its own buffer, else xc), the period's nis,
+// the closed-loop trajectory, the seam's host vectors, and which stages the periods go through.
+struct MpcState {
+    const Staged* a;
+    double *xp, *xc, *ym, *d_nis, *d_x_cl, *d_u_cl;
+    const double *u_min, *u_max, *sigma_y;
+    bool measured, filt, delayed, score;
+    long long rows;                            // plant steps of the run: the rows per instance of its arrays
+    size_t ym_n;
+};
+
+// everything before the first period
+static int mpc_begin(ilqr_handle* h, const MpcRun& r, MpcState& st) {
+    const Staged* a = st.a;
+    st.filt = r.est || r.sens; st.delayed = r.io && r.io->delay == 1; st.score = r.cl_cost != nullptr;
+    st.u_min = r.io ? r.io->u_min : nullptr; st.u_max = r.io ? r.io->u_max : nullptr; st.sigma_y = r.io ? r.io->sigma_y : nullptr;
+    st.rows = (long long)r.d->periods * r.d->steps; st.ym_n = r.sens ? (size_t)r.sens->ny : (size_t)h->L.nx;
+    st.xp = a[M_X].d();
+    st.xc = st.measured ? a[M_XC].d() : st.xp;
+    st.d_x_cl = a[M_X_CL].d(); st.d_u_cl = a[M_U_CL].d();
+    st.ym = st.filt ? a[M_YM].d() : st.xc;
+    st.d_nis = a[M_NIS].d();
+    const size_t row = (size_t)h->L.nx * 8;
+    if (!r.x0) HIP_TRY(hipMemcpy2DAsync(st.xp, row, h->ws + h->L.xb, (size_t)h->L.stride * 8, row, (size_t)h->B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
+    if (a[M_NONFINITE].p) HIP_TRY(hipMemsetAsync(a[M_NONFINITE].p, 0xff, a[M_NONFINITE].bytes, h->stream));       // -1: the plant kernel keeps the first mark
+    if (a[M_SATURATED].p) HIP_TRY(hipMemsetAsync(a[M_SATURATED].p, 0, a[M_SATURATED].bytes, h->stream));          // the plant kernel adds to it
+    if (st.filt && !r.xhat0) HIP_TRY(hipMemcpyAsync(st.xc, st.xp, a[M_XC].bytes, hipMemcpyDeviceToDevice, h->stream));           // x̂_0 = the first plant state
+    return ILQR_OK;
+}
+
+// the measurement at plant step `step`, the update with it and the estimate's move to the end of the period under the plan in
+// flight: the selection of state components, or the linear sensor
+static int mpc_measure(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t step) {
+    const ilqr_mpc_desc* d = r.d;
+    return r.sens ? measure_linear_launch(h, d->seed, d->first_instance, step, r.sens->ny, st.a[M_SENS_H].d(), st.a[M_SENS_SIGMA].d(), st.xp, st.ym)
+                  : measure_launch(h, d->seed, d->first_instance, step, st.sigma_y, st.xp, st.ym);
+}
+static int mpc_update(ilqr_handle* h, const MpcRun& r, const MpcState& st) {
+    return r.sens ? sensor_update_launch(h, r.sens->ny, 0, st.a[M_SENS_H].d(), st.a[M_SENS_R].d(), st.ym, nullptr, st.xc, st.a[M_P].d(), nullptr, st.d_nis, nullptr)
+                  : update_launch(h, r.est->measured, r.est->r, st.ym, st.xc, st.a[M_P].d(), nullptr, st.d_nis, nullptr);
+}
+static int mpc_predict(ilqr_handle* h, const MpcRun& r, const MpcState& st) {
+    return predict_launch(h, r.d->steps, r.d->plant_feedback, st.u_min, st.u_max, r.est ? r.est->q : r.sens->q, st.xc, st.a[M_P].d());
+}
+
+// the seam before the plant steps of period p: a delayed run only
+static int mpc_before_step(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t p) {
+    if (!st.delayed) return ILQR_OK;
+    const ilqr_mpc_desc* d = r.d;
+    ILQR_TRY(mpc_measure(h, r, st, p * d->steps));
+    if (st.filt) {
+        // the measurement of the state at p·k corrects the estimate, which then moves on to (p+1)·k under the plan in flight
+        ILQR_TRY(mpc_update(h, r, st));
+        return mpc_predict(h, r, st);
     }
-    if (measured) ILQR_TRY(grow(h, h->plant[PLANT_XC], B * n * 8));
-    if (filt) {                                    // the period's measurement and nis
-        ILQR_TRY(grow(h, h->plant[EST_Y], B * ym_n * 8));
-        ILQR_TRY(grow(h, h->plant[EST_NIS], B * 8));
+    // the solve of this period started one period ago: from a measurement of the state at p·k, moved on by the controller's
+    // own model under the plan in flight — same feedback and limits, no process noise, the handle's parameters, no outputs
+    return plant_launch(h, plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, nullptr, st.u_min, st.u_max), nullptr,
+                        st.xc, nullptr, nullptr, nullptr, nullptr);
+}
+
+// the plant steps of period p: rows p·k .. of the run's arrays
+static ilqr::PlantArgs mpc_plant_args(const ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t p) {
+    const ilqr_mpc_desc* d = r.d;
+    ilqr::PlantArgs a = plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, d->sigma_x, st.u_min, st.u_max);
+    a.w = st.a[M_W].d(); a.x = st.xp; a.x_out = st.d_x_cl; a.u_out = st.d_u_cl; a.nonfinite = st.a[M_NONFINITE].i();
+    a.saturated = st.a[M_SATURATED].i();
+    a.nf_global = 1;
+    a.w_ld = st.rows; a.x_ld = st.rows + 1; a.u_ld = st.rows;
+    a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
+    return a;
+}
+
+// the seam after them: the measurement of the new state and the filter (a run without delay), row p of y_cl and of the filter's logs
+static int mpc_after_step(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t p) {
+    const Staged* a = st.a;
+    const size_t B = (size_t)h->B, n = (size_t)h->L.nx, P = (size_t)r.d->periods;
+    if (st.measured && !st.delayed) ILQR_TRY(mpc_measure(h, r, st, (p + 1) * r.d->steps));
+    if (st.filt && !st.delayed) {                  // the estimate moves on to (p+1)·k under the plan in flight, then takes the measurement in
+        ILQR_TRY(mpc_predict(h, r, st));
+        ILQR_TRY(mpc_update(h, r, st));
     }
-    ILQR_TRY(stage_in(h, arrays));
-    double* xp = (double*)h->plant[PLANT_X].p;
-    double* xc = measured ? (double*)h->plant[PLANT_XC].p : xp;        // what the shift is handed: the controller's view of the plant state
-    double* d_x_cl = score ? (double*)h->plant[PLANT_X_OUT].p : s_x_cl.dev<double>();
-    double* d_u_cl = score ? (double*)h->plant[PLANT_U_OUT].p : s_u_cl.dev<double>();
-    const double* u_min = io ? io->u_min : nullptr;
-    const double* u_max = io ? io->u_max : nullptr;
-    const double* sigma_y = io ? io->sigma_y : nullptr;
-    const bool delayed = io && io->delay == 1;
-    if (!x0) HIP_TRY(hipMemcpy2DAsync(xp, n * 8, h->ws + h->L.xb, (size_t)h->L.stride * 8, n * 8, B, hipMemcpyDeviceToDevice, h->stream));     // x̄_0
-    if (s_nonfinite.bytes) HIP_TRY(hipMemsetAsync(s_nonfinite.st->p, 0xff, B * 4, h->stream));       // -1: the plant kernel keeps the first mark
-    if (s_saturated.bytes) HIP_TRY(hipMemsetAsync(s_saturated.st->p, 0, B * 4, h->stream));          // the plant kernel adds to it
-    double* ym = filt ? (double*)h->plant[EST_Y].p : xc;                 // where the measurement lands: with a filter xc is the estimate
-    double* d_nis = filt ? (double*)h->plant[EST_NIS].p : nullptr;
-    // the measurement at plant step `step` and the update with it: the selection of state components, or the linear sensor
-    const auto measure = [&](int32_t step, double* y) {
-        return sens ? measure_linear_launch(h, d->seed, d->first_instance, step, sens->ny, s_sens_H.dev<const double>(), s_sens_sigma.dev<const double>(),
-                                            xp, y)
-                    : measure_launch(h, d->seed, d->first_instance, step, sigma_y, xp, y);
-    };
-    const auto update = [&]() {
-        return sens ? sensor_update_launch(h, sens->ny, 0, s_sens_H.dev<const double>(), s_sens_r.dev<const double>(), ym, nullptr, xc,
-                                           s_P.dev<double>(), nullptr, d_nis, nullptr)
-                    : update_launch(h, est->measured, est->r, ym, xc, s_P.dev<double>(), nullptr, d_nis, nullptr);
-    };
-    const bool est_log = s_xhat_cl.bytes || s_pdiag_cl.bytes || s_nis_cl.bytes;
-    if (filt && !xhat0) HIP_TRY(hipMemcpyAsync(xc, xp, B * n * 8, hipMemcpyDeviceToDevice, h->stream));              // x̂_0 = the first plant state
-    for (int32_t p = 0; p < d->periods; ++p) {
-        if (delayed && filt) {
-            // the measurement of the state at p·k corrects the estimate, which then moves on to (p+1)·k under the plan in flight
-            ILQR_TRY(measure(p * d->steps, ym));
-            ILQR_TRY(update());
-            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, fq, xc, s_P.dev<double>()));
-        } else if (delayed) {
-            // the solve of this period started one period ago: from a measurement of the state at p·k, moved on by the controller's
-            // own model under the plan in flight — same feedback and limits, no process noise, the handle's parameters, no outputs
-            ILQR_TRY(measure_launch(h, d->seed, d->first_instance, p * d->steps, sigma_y, xp, xc));
-            ILQR_TRY(plant_launch(h, plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, nullptr, u_min, u_max),
-                                  nullptr, xc, nullptr, nullptr, nullptr, nullptr));
-        }
-        ilqr::PlantArgs a = plant_args(h, d->steps, d->plant_feedback, d->seed, d->first_instance, p * d->steps, d->sigma_x, u_min, u_max);
-        a.w = s_w.dev<const double>(); a.x = xp; a.x_out = d_x_cl; a.u_out = d_u_cl; a.nonfinite = s_nonfinite.dev<int32_t>();
-        a.saturated = s_saturated.dev<int32_t>();
-        a.nf_global = 1;
-        a.w_ld = (long long)R; a.x_ld = (long long)R + 1; a.u_ld = (long long)R;                     // rows p·k .. of the run's arrays
-        a.w_row0 = a.x_row0 = a.u_row0 = (long long)p * d->steps;
+    if (a[M_Y_CL].p)                               // row p of y_cl: what the controller is given, with a filter the measurement taken
+        HIP_TRY(hipMemcpy2DAsync(a[M_Y_CL].d() + (size_t)p * st.ym_n, P * st.ym_n * 8, st.ym, st.ym_n * 8, st.ym_n * 8, B, hipMemcpyDeviceToDevice, h->stream));
+    if (a[M_XHAT_CL].p || a[M_PDIAG_CL].p || a[M_NIS_CL].p) {
+        const unsigned grid = (unsigned)((B * n + 255) / 256);
+        hipLaunchKernelGGL(estimate_log_kernel, dim3(grid), dim3(256), 0, h->stream, (int)B, (int)n, r.d->periods, p, st.xc, a[M_P].d(), st.d_nis,
+                           a[M_XHAT_CL].d(), a[M_PDIAG_CL].d(), a[M_NIS_CL].d());
+        if (hipGetLastError() != hipSuccess) return fail(ILQR_ERR_HIP, "estimator log launch failed");
+    }
+    return ILQR_OK;
+}
+
+// the score of period p's steps — before the shift: it overwrites the θ rows 0 .. k−1 the plant ran under
+static int mpc_score(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t p) {
+    ilqr::ScoreArgs q = score_args(h, r.d->steps);
+    q.w = st.a[M_W].d(); q.x = st.d_x_cl; q.u = st.d_u_cl; q.cost = st.a[M_COST].d(); q.viol = st.a[M_VIOL].d();
+    q.w_ld = q.u_ld = q.cost_ld = q.viol_ld = st.rows; q.x_ld = st.rows + 1;
+    q.w_row0 = q.x_row0 = q.u_row0 = q.cost_row0 = q.viol_row0 = (long long)p * r.d->steps;
+    if (h->vt->launch_plant_score(&q, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant score launch failed");
+    return ILQR_OK;
+}
+
+// the re-solve of period p: the horizon shifted onto the controller's view of the plant state, the duals with it, the solve
+static int mpc_resolve(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t p) {
+    const ilqr_mpc_desc* d = r.d;
+    ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, st.xc, st.a[M_PREVIEW].d(), st.rows, (long long)p * d->steps));
+    if (d->warm) ILQR_TRY(ilqr_shift_duals_device(h, d->steps, d->duals_tail, d->duals_penalty));
+    return d->warm ? ilqr_solve_warm(h) : ilqr_solve(h);
+}
+
+// row p of the log: the solve's statistics beside the plant launch's arguments
+static int mpc_log_row(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t p) {
+    ilqr::PlantArgs a = mpc_plant_args(h, r, st, p);
+    a.log = st.a[M_LOG].d(); a.log_ld = r.d->periods; a.log_row = p;
+    if (h->vt->launch_mpc_log(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "log launch failed");
+    return ILQR_OK;
+}
+
+// the run on one handle whose instances start at `lo` of the caller's batch: the order of everything it enqueues
+static int mpc_enqueue(ilqr_handle* h, const MpcRun& run, bool measured, size_t lo, const Staged* arrays) {
+    ilqr_mpc_desc d = *run.d;
+    d.first_instance += (int64_t)lo;
+    MpcRun r = run;
+    r.d = &d;
+    MpcState st = {};
+    st.a = arrays; st.measured = measured;
+    ILQR_TRY(mpc_begin(h, r, st));
+    for (int32_t p = 0; p < d.periods; ++p) {
+        ILQR_TRY(mpc_before_step(h, r, st, p));
+        ilqr::PlantArgs a = mpc_plant_args(h, r, st, p);
         if (h->vt->launch_plant(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant step launch failed");
-        if (measured && !delayed) ILQR_TRY(measure((p + 1) * d->steps, ym));
-        if (filt && !delayed) {                    // the estimate moves on to (p+1)·k under the plan in flight, then takes the measurement in
-            ILQR_TRY(predict_launch(h, d->steps, d->plant_feedback, u_min, u_max, fq, xc, s_P.dev<double>()));
-            ILQR_TRY(update());
-        }
-        if (s_y_cl.bytes)                          // row p of y_cl: what the controller is given, with a filter the measurement taken
-            HIP_TRY(hipMemcpy2DAsync(s_y_cl.dev<double>() + (size_t)p * ym_n, P * ym_n * 8, ym, ym_n * 8, ym_n * 8, B, hipMemcpyDeviceToDevice, h->stream));
-        if (est_log) {
-            const unsigned grid = (unsigned)((B * n + 255) / 256);
-            hipLaunchKernelGGL(estimate_log_kernel, dim3(grid), dim3(256), 0, h->stream, (int)B, (int)n, d->periods, p, xc, s_P.dev<double>(), d_nis,
-                               s_xhat_cl.dev<double>(), s_pdiag_cl.dev<double>(), s_nis_cl.dev<double>());
-            if (hipGetLastError() != hipSuccess) return fail(ILQR_ERR_HIP, "estimator log launch failed");
-        }
-        if (score) {                               // before the shift: it overwrites the θ rows 0 .. k−1 the plant ran under
-            ilqr::ScoreArgs q = score_args(h, d->steps);
-            q.w = a.w; q.x = d_x_cl; q.u = d_u_cl; q.cost = s_cost.dev<double>(); q.viol = s_viol.dev<double>();
-            q.w_ld = q.u_ld = q.cost_ld = q.viol_ld = (long long)R; q.x_ld = (long long)R + 1;
-            q.w_row0 = q.x_row0 = q.u_row0 = q.cost_row0 = q.viol_row0 = a.x_row0;
-            if (h->vt->launch_plant_score(&q, h->stream) != 0) return fail(ILQR_ERR_HIP, "plant score launch failed");
-        }
-        ILQR_TRY(shift_launch(h, d->steps, d->shift_tail, d->shift_feedback, xc, s_preview.dev<const double>(), (long long)R, a.x_row0));
-        if (d->warm) ILQR_TRY(ilqr_shift_duals_device(h, d->steps, d->duals_tail, d->duals_penalty));
-        ILQR_TRY(d->warm ? ilqr_solve_warm(h) : ilqr_solve(h));
-        if (s_log.bytes) {
-            a.log = s_log.dev<double>(); a.log_ld = d->periods; a.log_row = p;
-            if (h->vt->launch_mpc_log(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "log launch failed");
-        }
+        ILQR_TRY(mpc_after_step(h, r, st, p));
+        if (st.score) ILQR_TRY(mpc_score(h, r, st, p));
+        ILQR_TRY(mpc_resolve(h, r, st, p));
+        if (arrays[M_LOG].p) ILQR_TRY(mpc_log_row(h, r, st, p));
     }
-    return stage_out(h, arrays);               // the one synchronise of the run
+    return ILQR_OK;
+}
+
+// Every entry point of the loop is this. With nothing measured (mpc_measured) the seam is skipped, with w_preview, cl_cost and
+// cl_violation null the preview and the score are: a null array has no bytes, no buffer and a null device pointer (run_staged), and
+// every stage of a period looks at its own flag of MpcState alone — so no launch, no buffer and no argument differs from the plainer
+// entry point's.
+static int mpc_run(ilqr_handle* h, const MpcRun& r) {
+    const bool measured = mpc_measured(r);
+    ILQR_TRY(mpc_check(h, r, measured));
+    if (!h->vt->launch_plant || !h->vt->launch_mpc_log) return fail(ILQR_ERR_MODEL, "this model module has no plant kernel");
+    if (r.cl_cost && !h->vt->launch_plant_score) return fail(ILQR_ERR_MODEL, "this model module has no plant score kernel");
+    if (measured && !h->vt->launch_plant_measure) return fail(ILQR_ERR_MODEL, "this model module has no measurement kernel");
+    if (r.est && (!h->vt->launch_estimate_predict || !h->vt->launch_estimate_update)) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
+    if (r.sens && (!h->vt->launch_estimate_predict || !h->vt->launch_sensor_update || !h->vt->launch_plant_measure_linear))
+        return fail(ILQR_ERR_MODEL, "this model module has no linear sensor kernel");
+    return run_staged(h, mpc_arrays(h, r, measured),
+                      [&](ilqr_handle* s, size_t lo, const Staged* arrays) { return mpc_enqueue(s, r, measured, lo, arrays); });
 }
 
 int ilqr_mpc_run(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, double* x_cl, double* u_cl, double* log,
                  int32_t* first_nonfinite) {
-    return mpc_run(h, d, nullptr, x0, w_plant, nullptr, x_cl, u_cl, log, first_nonfinite, nullptr, nullptr, nullptr, nullptr, "ilqr_mpc_run");
+    MpcRun r = {}; r.who = "ilqr_mpc_run"; r.d = d;
+    r.x0 = x0; r.w_plant = w_plant;
+    r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite;
+    return mpc_run(h, r);
 }
 
 int ilqr_mpc_run_preview(ilqr_handle* h, const ilqr_mpc_desc* d, const double* x0, const double* w_plant, const double* w_preview, double* x_cl,
                          double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation) {
-    return mpc_run(h, d, nullptr, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, nullptr, nullptr,
-                   "ilqr_mpc_run_preview");
+    MpcRun r = {}; r.who = "ilqr_mpc_run_preview"; r.d = d;
+    r.x0 = x0; r.w_plant = w_plant; r.w_preview = w_preview;
+    r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite; r.cl_cost = cl_cost; r.cl_violation = cl_violation;
+    return mpc_run(h, r);
 }
 
 int ilqr_mpc_run_io(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const double* x0, const double* w_plant, const double* w_preview,
                     double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl,
                     int32_t* saturated) {
-    return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_io");
+    MpcRun r = {}; r.who = "ilqr_mpc_run_io"; r.d = d; r.io = io;
+    r.x0 = x0; r.w_plant = w_plant; r.w_preview = w_preview;
+    r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite; r.cl_cost = cl_cost; r.cl_violation = cl_violation;
+    r.y_cl = y_cl; r.saturated = saturated;
+    return mpc_run(h, r);
 }
 
 int ilqr_mpc_run_est(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const ilqr_estimator* est, const double* x0, const double* xhat0,
                      double* P, const double* w_plant, const double* w_preview, double* x_cl, double* u_cl, double* log, int32_t* first_nonfinite,
                      double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl, double* pdiag_cl, double* nis_cl) {
-    return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_est", est,
-                   xhat0, P, xhat_cl, pdiag_cl, nis_cl);
+    MpcRun r = {}; r.who = "ilqr_mpc_run_est"; r.d = d; r.io = io; r.est = est;
+    r.x0 = x0; r.xhat0 = xhat0; r.Pcov = P; r.w_plant = w_plant; r.w_preview = w_preview;
+    r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite; r.cl_cost = cl_cost; r.cl_violation = cl_violation;
+    r.y_cl = y_cl; r.saturated = saturated; r.xhat_cl = xhat_cl; r.pdiag_cl = pdiag_cl; r.nis_cl = nis_cl;
+    return mpc_run(h, r);
 }
 
 int ilqr_mpc_run_sensor(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const ilqr_sensor* sensor, const double* x0,
                         const double* xhat0, double* P, const double* w_plant, const double* w_preview, double* x_cl, double* u_cl, double* log,
                         int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl,
                         double* pdiag_cl, double* nis_cl) {
-    return mpc_run(h, d, io, x0, w_plant, w_preview, x_cl, u_cl, log, first_nonfinite, cl_cost, cl_violation, y_cl, saturated, "ilqr_mpc_run_sensor",
-                   nullptr, xhat0, P, xhat_cl, pdiag_cl, nis_cl, sensor);
+    MpcRun r = {}; r.who = "ilqr_mpc_run_sensor"; r.d = d; r.io = io; r.sens = sensor;
+    r.x0 = x0; r.xhat0 = xhat0; r.Pcov = P; r.w_plant = w_plant; r.w_preview = w_preview;
+    r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite; r.cl_cost = cl_cost; r.cl_violation = cl_violation;
+    r.y_cl = y_cl; r.saturated = saturated; r.xhat_cl = xhat_cl; r.pdiag_cl = pdiag_cl; r.nis_cl = nis_cl;
+    return mpc_run(h, r);
 }
 
 int ilqr_set_kernel_variant(ilqr_handle* h, int32_t variant) {

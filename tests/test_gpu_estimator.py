@@ -12,7 +12,7 @@ max(1, max |reference|) is the project's own (tests/test_estimator_ref.py: the y
 6. mpc_run_(estimator=...) is, bit for bit, the device entry points called one by one (delay 0 and 1; acrobot and synth12), and its
    xhat and pdiag are the yardstick loop's within TOL_XU when that loop is fed the device's own plans.
 7. estimator=None is mpc_run_ bit for bit.
-8. A sharded handle [0, 0] equals the single one.
+8. A sharded handle [0, 0] equals the single one, also with every input and output array of the loop passed at once.
 9. It filters: acrobot, positions measured — the estimate beats the measurement on the positions and prediction alone on the
    velocities (the conditions tests/test_estimator_ref.py shows on the yardstick with a factor of two to spare)."""
 import numpy as np
@@ -275,6 +275,27 @@ def test_sharded_handle_equals_the_single_one(pkg, delay):
         two.estimate_predict_device_(1, 1)
     with pytest.raises(pkg._ffi.IlqrError, match="sharded"):
         two.estimate_update_device_(1, 1, 1, E.r(n))
+    one.close(); two.close()
+
+
+def test_sharded_loop_with_every_array_equals_the_single_one(pkg):
+    """every input and output array of ilqr_mpc_run_est at once: each is sliced per shard (B = 7: shards of 4 and 3)"""
+    B, periods, k = 7, 2, 2
+    one, w = _solved(pkg, "car_obs", B)
+    two, _ = _solved(pkg, "car_obs", B, devices=[0, 0])
+    n = one.nx
+    x0 = R.plant_starts(one.get_trajectory()[0])
+    xh, Ps, _ = _inputs(one)
+    u_min, u_max = IO.LIMITS["car_obs"]
+    wp = R.plant_parameters(w, periods * k)
+    est = dict(measured=E.masks("car_obs", n)[0], q=E.q(n), r=E.r(n), xhat0=xh, P0=Ps)
+    r1, r2 = (s.mpc_run_(periods, k, x0=x0, plant_feedback=True, sigma_x=R.sigma_x(n), seed=R.SEED, first_instance=11, w_plant=wp,
+                         w_preview=np.ascontiguousarray(wp[:, ::-1]), score=True, u_min=u_min, u_max=u_max, sigma_y=IO.sigma_y(n), estimator=est)
+              for s in (one, two))
+    for key in ("x", "u", "first_nonfinite", "cl_cost", "cl_violation", "y_cl", "saturated", "xhat", "pdiag", "nis", "P"):
+        assert np.array_equal(getattr(r1, key), getattr(r2, key), equal_nan=True), key
+    for f in r1.log:
+        assert np.array_equal(r1.log[f], r2.log[f], equal_nan=True), f
     one.close(); two.close()
 
 

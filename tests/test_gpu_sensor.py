@@ -16,7 +16,8 @@ agree within a tenth of it).
 6. mpc_run_(estimator=dict(H=...)) is, bit for bit, the device entry points called one by one (delay 0 and 1; acrobot and synth12),
    and its xhat and pdiag are the yardstick loop's within TOL_XU when that loop is fed the device's own plans.
 7. Without H mpc_run_ is what it was; with sensor NULL ilqr_mpc_run_sensor is ilqr_mpc_run_io.
-8. A sharded handle [0, 0] equals the single one; the device forms are refused on it.
+8. A sharded handle [0, 0] equals the single one, also with a shared H and with every input and output array of the loop passed at
+   once; the device forms are refused on it.
 9. It filters: acrobot, H = [[1,0,0,0],[1,1,0,0]] — the estimate beats the raw encoders on both angles and prediction alone on the
    velocities (the conditions tests/test_sensor_ref.py shows on the yardstick with a factor of two to spare)."""
 import numpy as np
@@ -393,6 +394,32 @@ def test_sharded_handle_equals_the_single_one(pkg, delay):
         two.estimate_update_linear_device_(1, 1, 1, 1, ny, S.r(ny))
     with pytest.raises(pkg._ffi.IlqrError, match="sharded"):
         two.plant_measure_linear_device_(1, 1, 1, ny)
+    one.close(); two.close()
+
+
+def test_sharded_loop_with_every_array_equals_the_single_one(pkg):
+    """every input and output array of ilqr_mpc_run_sensor at once, and the update with an H the batch shares (it is not sliced):
+    B = 7 (shards of 4 and 3), ny = 3"""
+    B, periods, k = 7, 2, 2
+    one, w = _solved(pkg, "car_obs", B)
+    two, _ = _solved(pkg, "car_obs", B, devices=[0, 0])
+    n, ny = one.nx, 3
+    x0 = R.plant_starts(one.get_trajectory()[0])
+    xh, Ps, ys = _inputs(one)
+    H = S.sensors(n, ny, B)[1]
+    y = S.readings(H, ys)
+    u1, u2 = (s.estimate_update_linear_(xh, Ps, y, H, S.r(ny)) for s in (one, two))
+    for key in u1:
+        assert np.array_equal(u1[key], u2[key]), key
+    u_min, u_max = IO.LIMITS["car_obs"]
+    wp = R.plant_parameters(w, periods * k)
+    est = dict(H=H, q=E.q(n), r=S.r(ny), sigma_y=S.sigma_y(ny), xhat0=xh, P0=Ps)
+    r1, r2 = (s.mpc_run_(periods, k, x0=x0, plant_feedback=True, sigma_x=R.sigma_x(n), seed=R.SEED, first_instance=11, w_plant=wp,
+                         w_preview=np.ascontiguousarray(wp[:, ::-1]), score=True, u_min=u_min, u_max=u_max, estimator=est) for s in (one, two))
+    for key in ("x", "u", "first_nonfinite", "cl_cost", "cl_violation", "y_cl", "saturated", "xhat", "pdiag", "nis", "P"):
+        assert np.array_equal(getattr(r1, key), getattr(r2, key), equal_nan=True), key
+    for f in r1.log:
+        assert np.array_equal(r1.log[f], r2.log[f], equal_nan=True), f
     one.close(); two.close()
 
 
