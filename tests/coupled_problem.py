@@ -2,7 +2,8 @@
 plain callables f(x, u) that both the product's symbolic constructors (Cost / Constraint of iterativelqr.jl_amd/codegen.py) and the
 independent restatement's (tests/golden/reference_restatement.py) accept.
 
-The dynamics are the synth family's (models.synth_nm / reference_restatement.synth32_problem), the base cost is theirs
+The dynamics are the synth family's (models.synth_nm / reference_restatement.synth32_problem; tests/coupled_dynamics.py is the
+family with coupled DYNAMICS), the base cost is theirs
 (0.1 Σ(x_i − x_g)² + 0.01 Σ u_j², terminal 10 Σ(x_i − x_g)²) and the base constraint is the action box. On top, each a convex
 function of an affine form (so the cost Hessian stays positive semidefinite and 0.01·I keeps Quu factorable), except the small
 bilinear e·u_0·u_{m−1}, which the 2(0.01 + a) on the diagonal of guu dominates:

@@ -2,7 +2,8 @@
 // tests/test_model_compile_host.py: no hipcc, no libilqr_hip.so, no GPU. argv: the C source of synth12, a scratch directory.
 // Prints one line per check and exits non-zero on the first that fails.
 // Second form, run by tests/test_coupled_problem.py: --probe, a scratch directory, then pairs of files — the C callables of a model
-// and the compact Hessian row expected of the probe ("nx nu nc_stage", "nxx nuu nux", the indices, the tile starts).
+// and the compact Hessian row expected of the probe ("nx nu nc_stage", "nxx nuu nux", the indices, the tile starts; a fifth line, where
+// tests/test_coupled_dynamics.py gives one: the state-dependent Jacobian entries, indices into [fx (nx*nx) | fu (nx*nu)], both column-major).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -58,16 +59,17 @@ static int probe_given_models(int argc, char** argv) {
         text << std::ifstream(argv[a]).rdbuf();
         const std::string source = text.str();
         std::ifstream expect(argv[a + 1]);
-        std::string l0, l1, l2, l3;
-        std::getline(expect, l0); std::getline(expect, l1); std::getline(expect, l2); std::getline(expect, l3);
+        std::string l0, l1, l2, l3, l4;
+        std::getline(expect, l0); std::getline(expect, l1); std::getline(expect, l2); std::getline(expect, l3); std::getline(expect, l4);
         const std::vector<int> dims = ints(l0), sizes = ints(l1), idx = ints(l2), starts = ints(l3);
         CHECK(dims.size() == 3 && sizes.size() == 3 && (int)idx.size() == sizes[0] + sizes[1] + sizes[2]);
         ilqr_model_source src = {"coupled_host", dims[0], dims[1], 0, dims[2], 0, (1ull << dims[2]) - 1, 0, source.c_str(), 0};
         const ModelStructure ms = probe_model_structure(&src, dir, "coupled", ProbeHints());
         CHECK(ms.found);
-        CHECK(ms.nxx == sizes[0] && ms.nuu == sizes[1] && ms.nux == sizes[2] && ms.nux > 0);
+        CHECK(ms.nxx == sizes[0] && ms.nuu == sizes[1] && ms.nux == sizes[2] && (ms.nux > 0 || !l4.empty()));
         CHECK(ms.hess_idx == idx);
         CHECK(ms.tile_start == starts);
+        if (!l4.empty()) CHECK(ms.jac_var == ints(l4));
     }
     std::printf("%d checks passed\n", checks);
     return 0;

@@ -1,6 +1,7 @@
 """GPU: coupled and state-dependent cost Hessians on every kernel family, against the independent restatement run live.
 
-Every other model of the GPU suite has diagonal, constant cost Hessians and (one equality row of car_tv aside) a zero gux. The
+Every other model of the GPU suite has diagonal, constant cost Hessians and (one equality row of car_tv aside) a zero gux (the
+dynamics counterpart, state-coupled Jacobians, is tests/test_gpu_coupled_dynamics.py). The
 family of tests/coupled_problem.py has a rectangular gux, off-diagonal gxx / guu, Hessians that depend on x and u (so that the
 reference's accumulation, hessian[t] .+= ..., src/costs.jl:74-80, SURVEY quirk Q1, is not "k times one number"), an off-diagonal
 terminal gxx and two coupled inequality rows whose Gauss-Newton term cuᵀ Iρ cx lands in gux (src/gradients.jl:79).

@@ -33,6 +33,14 @@ def main(verbose=True):
         import coupled_problem as CP
         for probe in (True, False):
             jobs.append((b"coupled12_c", (12, 5, 0, 12, 0, (1 << 12) - 1, 0), CP.c_source(pkg, 12, 5).encode(), probe))
+    # the coupled-dynamics family of tests/coupled_dynamics.py the same way: (12, 5) and (17, 3) as C callables, probed and dense
+    CD = None
+    if os.path.exists(os.path.join(ROOT, "tests", "coupled_dynamics.py")):
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import coupled_dynamics as CD
+        for n, m in CD.C_SIZES:
+            for probe in (True, False):
+                jobs.append(((CD.name(n, m) + "_c").encode(), CD.c_dims(n, m), CD.c_source(pkg, n, m).encode(), probe))
     old = os.environ.get("ILQR_NO_STRUCTURE_PROBE")
     try:
         for name, dims, text, probe in jobs:
@@ -63,6 +71,10 @@ def main(verbose=True):
         lowered = []
         for n, m, T, con in sorted(set((n, m, 11, con) for n, m, _, con in (CP.CASES if CP else []))):       # (the horizon does not enter the module)
             dyn, costs, cons, name = CP.product_problem(pkg, n, m, T, con)
+            low = pkg.lowering.lower(dyn, costs, cons)
+            lowered.append((name, low["dynamics"], low["cost_stage"], low["cost_term"], low["con_stage"], low["con_term"]))
+        for n, m in (CD.SIZES if CD else []):
+            dyn, costs, cons, name = CD.product_problem(pkg, n, m)
             low = pkg.lowering.lower(dyn, costs, cons)
             lowered.append((name, low["dynamics"], low["cost_stage"], low["cost_term"], low["con_stage"], low["con_term"]))
         with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as pool:
