@@ -578,8 +578,8 @@ int ilqr_plant_measure_linear_device(ilqr_handle* h, uint64_t seed, int64_t firs
  * before the first launch. With sensor NULL the call is ilqr_mpc_run_io: no launch, buffer or argument differs. Refused
  * (ILQR_ERR_INVALID) before any launch: everything ilqr_mpc_run_io, ilqr_estimate_predict and the two calls above refuse;
  * io->sigma_y non-null together with a sensor (the sensor's own [ny] array replaces it); a sensor with P NULL; xhat0, P, xhat_cl,
- * pdiag_cl or nis_cl without a sensor. Works on a sharded handle. Not offered: a non-diagonal R, a nonlinear h(x, w) generated into
- * the model, an H that varies with time inside the loop, outlier gating. */
+ * pdiag_cl or nis_cl without a sensor. Works on a sharded handle. Not offered: a non-diagonal R, an H that varies with time inside
+ * the loop, outlier gating. (A nonlinear h(x, s): ilqr_compile_sensor and ilqr_mpc_run_nlsensor below.) */
 typedef struct {
     int32_t ny, reserved;
     const double* H;           /* HOST [ny][nx], shared by the batch */
@@ -594,6 +594,115 @@ int ilqr_mpc_run_sensor(ilqr_handle* h, const ilqr_mpc_desc* d,
                         double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation,       /* as ilqr_mpc_run_est's */
                         double* y_cl,              /* NULL, or [B][P][ny] */
                         int32_t* saturated, double* xhat_cl, double* pdiag_cl, double* nis_cl);
+
+/* A NONLINEAR sensor y = h(x, s) + v, v ~ N(0, diag(r)), for the filter and the loop: a range, a bearing, a camera pixel, sin(q) of an
+ * encoder. The sensor is a compiled module of its own, apart from the model (one model runs with several sensors): nx inputs,
+ * 1 <= ny <= 64 outputs (ny may exceed nx), 0 <= ns <= 64 sensor parameters s — beacon positions, a focal length — shared by the batch,
+ * [ns] (per_instance_s == 0), or one row per instance, [B][ns] (per_instance_s == 1).
+ *
+ * ilqr_compile_sensor: `source` is C code that defines ONE function, row-wise so that no thread ever holds ny · nx numbers,
+ *     ILQR_SENSOR_FN void sensor_row(int j, double* y, double* dydx, const double* x, const double* s);
+ * which writes *y = h_j(x, s) and dydx[k] = dh_j/dx_k for k < nx; dydx is pre-zeroed by the caller, so only non-zero partials need be
+ * written; math.h names and ilqr::sincos_fast are available as in model sources. The library wraps the source
+ * (csrc/ilqr_sensor_adapter.hpp; floating-point contraction is off around it, so h_j is the same bits wherever it is evaluated),
+ * compiles it for gfx950 with hipcc as a child process as ilqr_compile_model does — cached under a hash of source, name, dimensions,
+ * the sensor ABI version and the library's kernel headers and flags, as lib/models/libilqr_sensor_<name>_c<tag>.so; temporary files
+ * under process-unique names, the module moved into place atomically — loads it and returns the registered name
+ * <name>_c<tag> and the module path. ilqr_load_sensor_library loads a module some process compiled earlier (no compiler needed).
+ * Refused (ILQR_ERR_INVALID): a null argument; a name that is not a C identifier; nx outside 1 .. 64, ny outside 1 .. 64, ns outside
+ * 0 .. 64; output buffers that are too small.
+ *
+ * ilqr_sensor_linearise: H_out[b][j][0 .. nx) = row j of dh/dx at x_lin[b], layout [B][ny][nx] row-major — what
+ * ilqr_estimate_update_linear reads with per_instance_H == 1; yhat_out[b][j] = h_j(x_lin[b], s), or with x_prior given
+ *     yhat_out[b][j] = h_j + SUM_k H_jk (x_prior[b][k] - x_lin[b][k]),
+ * one FMA chain over ascending k = 0 .. nx-1 that starts from h_j, each difference rounded first: the reference output of an
+ * iterated filter whose prior is x_prior.
+ * ilqr_plant_measure_sensor: y[b][j] = h_j(x[b], s), then + sigma_y[j] · z(seed, first_instance + b, 5 + j / 16, step, j % 16) where
+ * sigma_y[j] != 0, product and sum rounded separately; z, the key fields 5 .. 8 and the host twin ilqr_candidate_noise(seed,
+ * first_instance, B, 9, step + 1, 16, z) are ilqr_plant_measure's, shared on purpose as the linear sensor shares them. With sigma_y
+ * NULL y is bit for bit the yhat of ilqr_sensor_linearise at x.
+ * ilqr_estimate_update_sensor, the measurement update of the extended Kalman filter with this sensor. iterations == 1: bit for
+ * bit ilqr_sensor_linearise_device(x_lin = xhat, x_prior = NULL) into H and yhat buffers the handle owns and reuses, followed by
+ * ilqr_estimate_update_linear_device(ny, per_instance_H = 1, H, r, y, yhat, ...): the existing update, untouched. iterations = N,
+ * 2 <= N <= 8, the ITERATED filter: the prior (x0, P0) = (xhat, P) on entry is kept in buffers of the handle; iteration 0 is the
+ * above; iteration i >= 1 linearises at the estimate iteration i-1 left with x_prior = x0, restores xhat <- x0 and P <- P0, and runs
+ * the same update — whose c_j = yhat_j - h_j·x0 is then exactly the offset of the Gauss-Newton IEKF. The outputs are the last
+ * iteration's.
+ *
+ * Refused (ILQR_ERR_INVALID) before any launch: a sensor name that is not registered; a sensor whose nx is not the handle's;
+ * per_instance_s other than 0 or 1; a null s with ns > 0; a non-finite entry of an s given on the host; iterations outside 1 .. 8;
+ * everything ilqr_estimate_update_linear and ilqr_plant_measure_linear refuse for the same arguments (a null array, an r entry that
+ * is not finite and > 0, a negative or non-finite sigma_y entry, step and first_instance outside the noise key's fields). Host
+ * forms: every array a host array; work on a sharded handle; synchronous. Device forms: s, x_lin, x_prior, H_out, yhat_out, x, y,
+ * xhat, P, innovation, nis, first_bad device pointers; r and sigma_y stay host arrays of ny doubles that travel as
+ * ilqr_estimate_update_linear_device's do and are read when the call is made; asynchronous on the handle's stream; refused on a
+ * sharded handle. */
+typedef struct {
+    const char* name;        /* C identifier */
+    int32_t nx, ny, ns;      /* inputs, outputs, sensor parameters */
+    const char* source;
+    int32_t flags;           /* 0 */
+} ilqr_sensor_source;
+int ilqr_compile_sensor(const ilqr_sensor_source* src, char* registered_name, size_t name_len, char* library_path, size_t path_len);
+int ilqr_load_sensor_library(const char* path);
+/* Sensor registry (compiled sensor modules call ilqr_register_sensor from a static initialiser; vtable: a
+ * const struct ilqr_sensor_vtable*, csrc/ilqr_device_sensor_nl.hpp). */
+int ilqr_register_sensor(const void* vtable);
+int ilqr_sensor_count(void);
+const char* ilqr_sensor_name(int32_t i);
+int ilqr_sensor_dims(const char* sensor, int32_t* nx, int32_t* ny, int32_t* ns);
+int ilqr_sensor_linearise(ilqr_handle* h, const char* sensor, int32_t per_instance_s,
+                          const double* s,                 /* NULL (ns == 0), [ns] or [B][ns] */
+                          const double* x_lin,             /* [B][nx] */
+                          const double* x_prior,           /* NULL, or [B][nx] */
+                          double* H_out,                   /* [B][ny][nx] */
+                          double* yhat_out);               /* [B][ny] */
+int ilqr_sensor_linearise_device(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* d_s, const double* d_x_lin,
+                                 const double* d_x_prior, double* d_H_out, double* d_yhat_out);
+int ilqr_plant_measure_sensor(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, uint64_t seed,
+                              int64_t first_instance, int32_t step,
+                              const double* sigma_y,       /* HOST, NULL or [ny], finite, >= 0 */
+                              const double* x,             /* [B][nx] */
+                              double* y);                  /* [B][ny] */
+int ilqr_plant_measure_sensor_device(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* d_s, uint64_t seed,
+                                     int64_t first_instance, int32_t step, const double* sigma_y, const double* d_x, double* d_y);
+int ilqr_estimate_update_sensor(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, int32_t iterations,
+                                const double* r,           /* HOST [ny], finite, > 0 */
+                                const double* y,           /* [B][ny] */
+                                double* xhat,              /* [B][nx] in / out */
+                                double* P,                 /* [B][nx][nx] in / out */
+                                double* innovation,        /* NULL, or [B][ny] */
+                                double* nis,               /* NULL, or [B] */
+                                int32_t* first_bad);       /* NULL, or [B] */
+int ilqr_estimate_update_sensor_device(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* d_s, int32_t iterations,
+                                       const double* r, const double* d_y, double* d_xhat, double* d_P, double* d_innovation, double* d_nis,
+                                       int32_t* d_first_bad);
+
+/* ilqr_mpc_run_sensor's loop with the nonlinear sensor: the measurement launch is ilqr_plant_measure_sensor_device(sensor, s,
+ * sigma_y) at the same step index, and the update ilqr_estimate_update_sensor_device(sensor, s, iterations, r) with the period's
+ * measurement. The order of the four calls per delay, the time update (with q), xc = xhat, y_cl [B][P][ny], xhat_cl, pdiag_cl and
+ * nis_cl stay ilqr_mpc_run_est's. s (per instance where ns_per_instance == 1: [B][ns]), r and sigma_y are copied to the device once,
+ * before the first launch; H, yhat and the prior's buffers too are grown before it; still one enqueue and one synchronise. With
+ * sensor NULL the call is ilqr_mpc_run_io: no launch, buffer or argument differs. Refused (ILQR_ERR_INVALID) before any launch:
+ * everything ilqr_mpc_run_sensor refuses for the same arguments (io->sigma_y together with a sensor among it) and everything
+ * ilqr_estimate_update_sensor and ilqr_plant_measure_sensor refuse. Works on a sharded handle. Not offered: a sensor that reads the
+ * model's parameters theta_t; an s that varies with time inside the loop; a non-diagonal R; outlier gating. */
+typedef struct {
+    const char* sensor;        /* registered name (ilqr_compile_sensor) */
+    int32_t ns_per_instance;   /* 0: s [ns] shared by the batch; 1: s [B][ns] */
+    const double* s;           /* HOST, NULL where ns == 0 */
+    const double* r;           /* HOST [ny] */
+    const double* q;           /* HOST, NULL or [nx] */
+    const double* sigma_y;     /* HOST, NULL or [ny] */
+    int32_t iterations;        /* 1 .. 8; 1: the extended Kalman filter, more: the iterated one */
+} ilqr_nl_sensor;
+int ilqr_mpc_run_nlsensor(ilqr_handle* h, const ilqr_mpc_desc* d,
+                          const ilqr_plant_io* io,        /* NULL: none */
+                          const ilqr_nl_sensor* sensor,   /* NULL: ilqr_mpc_run_io */
+                          const double* x0, const double* xhat0, double* P, const double* w_plant, const double* w_preview, double* x_cl,
+                          double* u_cl, double* log, int32_t* first_nonfinite, double* cl_cost, double* cl_violation,     /* as ilqr_mpc_run_est's */
+                          double* y_cl,                   /* NULL, or [B][P][ny] */
+                          int32_t* saturated, double* xhat_cl, double* pdiag_cl, double* nis_cl);
 
 /* Stage-level entry points for parity tests (one kernel each, mode = :nominal):
  * the reference functions they run are listed per id. */

@@ -79,6 +79,25 @@ class ilqr_sensor(C.Structure):
 
 
 Sensor = ilqr_sensor
+
+
+class ilqr_sensor_source(C.Structure):
+    """ilqr_sensor_source: a nonlinear sensor y = h(x, s) as C source of its row-wise callable sensor_row (ilqr_compile_sensor)."""
+    _fields_ = [("name", C.c_char_p), ("nx", C.c_int32), ("ny", C.c_int32), ("ns", C.c_int32), ("source", C.c_char_p), ("flags", C.c_int32)]
+
+
+SensorSource = ilqr_sensor_source
+
+
+class ilqr_nl_sensor(C.Structure):
+    """ilqr_nl_sensor: the compiled nonlinear sensor of ilqr_mpc_run_nlsensor — its registered name, whether s is [B][ns], the
+    iterations of the update, s, the diagonal of R [ny], the diagonal of Q [nx] and the measurement noise [ny] (host arrays the caller
+    keeps alive over the call)."""
+    _fields_ = [("sensor", C.c_char_p), ("ns_per_instance", C.c_int32), ("s", c_double_p), ("r", c_double_p), ("q", c_double_p),
+                ("sigma_y", c_double_p), ("iterations", C.c_int32)]
+
+
+NlSensor = ilqr_nl_sensor
 MPC_LOG_W = 9
 MPC_LOG_COLUMNS = ("objective", "gradient_norm", "max_violation", "step_size", "iterations", "outer_iterations", "status", "potrf_info",
                    "rollouts")
@@ -204,6 +223,24 @@ SYMBOLS = {
     "ilqr_mpc_run_sensor": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), C.POINTER(Sensor), c_double_p, c_double_p, c_double_p,
                                       c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
                                       c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
+    "ilqr_compile_sensor": (C.c_int, [C.POINTER(SensorSource), C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]),
+    "ilqr_load_sensor_library": (C.c_int, [C.c_char_p]),
+    "ilqr_register_sensor": (C.c_int, [C.c_void_p]),
+    "ilqr_sensor_count": (C.c_int, []),
+    "ilqr_sensor_name": (C.c_char_p, [C.c_int32]),
+    "ilqr_sensor_dims": (C.c_int, [C.c_char_p, c_int32_p, c_int32_p, c_int32_p]),
+    "ilqr_sensor_linearise": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "ilqr_sensor_linearise_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32] + [C.c_void_p] * 5),
+    "ilqr_plant_measure_sensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, c_double_p, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p,
+                                            c_double_p]),
+    "ilqr_plant_measure_sensor_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_int64, C.c_int32, c_double_p,
+                                                   C.c_void_p, C.c_void_p]),
+    "ilqr_estimate_update_sensor": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_double_p,
+                                              c_double_p, c_double_p, C.POINTER(C.c_int32)]),
+    "ilqr_estimate_update_sensor_device": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, c_double_p] + [C.c_void_p] * 6),
+    "ilqr_mpc_run_nlsensor": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), C.POINTER(NlSensor), c_double_p, c_double_p, c_double_p,
+                                        c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
+                                        c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
     "ilqr_solve":(C.c_int, [C.c_void_p]),
     "ilqr_solve_warm": (C.c_int, [C.c_void_p]),
     "ilqr_synchronize": (C.c_int, [C.c_void_p]),

@@ -142,6 +142,30 @@ def compile_model(name, dynamics, cost_stage, cost_term, con_stage=None, con_ter
     return uname, so
 
 
+def compile_sensor_source(name, nx, ny, ns, source):
+    """C source of a sensor's `sensor_row` (written by hand, or generate_sensor_source's) -> sensor module (ilqr_compile_sensor:
+    hipcc as a child process, cached in lib/models). Returns (registered_name, path)."""
+    reg, path = C.create_string_buffer(256), C.create_string_buffer(4096)
+    src = _ffi.SensorSource(name.encode(), int(nx), int(ny), int(ns), source.encode(), 0)
+    _ffi.check(_ffi.lib().ilqr_compile_sensor(C.byref(src), reg, len(reg), path, len(path)))
+    return reg.value.decode(), path.value.decode()
+
+
+def compile_sensor(name, h, nx, ns=0):
+    """A nonlinear sensor y = h(x, s) from a Python function on sympy symbols (x: nx states, s: ns sensor parameters; returns the ny
+    outputs): traced, differentiated and emitted row-wise by codegen.generate_sensor_source, compiled by ilqr_compile_sensor.
+    Returns (registered_name, path); the name is what the Solver's sensor methods and mpc_run_(estimator=dict(sensor=...)) take."""
+    ny, src = codegen.generate_sensor_source(name, h, nx, ns)
+    return compile_sensor_source(name, nx, ny, ns, src)
+
+
+def sensor_dims(sensor):
+    """(nx, ny, ns) of a registered sensor"""
+    d = [C.c_int32() for _ in range(3)]
+    _ffi.check(_ffi.lib().ilqr_sensor_dims(sensor.encode(), *[C.byref(v) for v in d]))
+    return tuple(v.value for v in d)
+
+
 class Solver:
     """Solver(dynamics, costs[, constraints]; options) — src/solver.jl:11-46 — for a batch.
 
@@ -521,6 +545,91 @@ class Solver:
                                                                _nul(sigma_y), C.c_void_p(d_x_ptr),
                                                                C.c_void_p(d_y_ptr)))
 
+    def _nl_sensor(self, sensor, s, r=None, sigma_y=None):
+        """a compiled sensor's arguments: (name bytes, ny, per_instance_s, s or None, r, sigma_y) — s [ns] shared or [B, ns]"""
+        _, ny, ns = sensor_dims(sensor)
+        per = 0
+        if s is not None:
+            s = np.ascontiguousarray(s, dtype=np.float64)
+            if s.shape == (self.B, ns) and s.ndim == 2:
+                per = 1
+            elif s.shape != (ns,):
+                raise ValueError("s must have shape [ns] or [B, ns]")
+            if ns == 0:
+                s = None
+        vec = lambda v: None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (ny,)))
+        return sensor.encode(), ny, per, s, vec(r), vec(sigma_y)
+
+    def sensor_linearise_(self, sensor, x_lin, s=None, x_prior=None):
+        """A compiled nonlinear sensor y = h(x, s) (compile_sensor) linearised on the device (ilqr_sensor_linearise) at x_lin [B, nx]:
+        returns (H [B, ny, nx] = ∂h/∂x there, yhat [B, ny] = h(x_lin, s)); with x_prior [B, nx], yhat = h + H (x_prior − x_lin), the
+        reference output of an iterated filter. s [ns] shared by the batch or [B, ns]."""
+        name, ny, per, s, _, _ = self._nl_sensor(sensor, s)
+        x_lin = np.ascontiguousarray(x_lin, dtype=np.float64)
+        if x_lin.shape != (self.B, self.nx):
+            raise ValueError("x_lin must have shape [B, nx]")
+        if x_prior is not None:
+            x_prior = np.ascontiguousarray(x_prior, dtype=np.float64)
+            if x_prior.shape != (self.B, self.nx):
+                raise ValueError("x_prior must have shape [B, nx]")
+        H, yhat = np.empty((self.B, ny, self.nx)), np.empty((self.B, ny))
+        _ffi.check(_ffi.lib().ilqr_sensor_linearise(self._h, name, per, _nul(s), _p(x_lin), _nul(x_prior), _p(H), _p(yhat)))
+        return H, yhat
+
+    def sensor_linearise_device_(self, sensor, d_x_lin_ptr, d_H_ptr, d_yhat_ptr, d_s_ptr=None, per_instance_s=False, d_x_prior_ptr=None):
+        """The same with raw device pointers on the handle's device, s among them; asynchronous on the handle's stream."""
+        _ffi.check(_ffi.lib().ilqr_sensor_linearise_device(self._h, sensor.encode(), 1 if per_instance_s else 0, _vp(d_s_ptr), _vp(d_x_lin_ptr),
+                                                           _vp(d_x_prior_ptr), _vp(d_H_ptr), _vp(d_yhat_ptr)))
+
+    def plant_measure_sensor_(self, sensor, x, s=None, step=0, sigma_y=None, seed=0, first_instance=0):
+        """What a compiled nonlinear sensor reads of the plant states x [B, nx] (ilqr_plant_measure_sensor): y = h(x, s), plus
+        sigma_y[j] · z where sigma_y[j] != 0 — plant_measure_'s stream. Returns y [B, ny]."""
+        name, ny, per, s, _, sigma_y = self._nl_sensor(sensor, s, None, sigma_y)
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.shape != (self.B, self.nx):
+            raise ValueError("x must have shape [B, nx]")
+        y = np.empty((self.B, ny))
+        _ffi.check(_ffi.lib().ilqr_plant_measure_sensor(self._h, name, per, _nul(s), int(seed), int(first_instance), int(step), _nul(sigma_y),
+                                                        _p(x), _p(y)))
+        return y
+
+    def plant_measure_sensor_device_(self, sensor, d_x_ptr, d_y_ptr, d_s_ptr=None, per_instance_s=False, step=0, sigma_y=None, seed=0,
+                                     first_instance=0):
+        """The same with raw device pointers on the handle's device for x, y and s; sigma_y stays a host array; asynchronous on the
+        handle's stream."""
+        _, ny, _ = sensor_dims(sensor)
+        if sigma_y is not None:
+            sigma_y = np.ascontiguousarray(np.broadcast_to(np.asarray(sigma_y, dtype=np.float64), (ny,)))
+        _ffi.check(_ffi.lib().ilqr_plant_measure_sensor_device(self._h, sensor.encode(), 1 if per_instance_s else 0, _vp(d_s_ptr), int(seed),
+                                                               int(first_instance), int(step), _nul(sigma_y), _vp(d_x_ptr), _vp(d_y_ptr)))
+
+    def estimate_update_sensor_(self, xhat, P, y, sensor, r, s=None, iterations=1):
+        """The measurement update of the extended Kalman filter with a compiled nonlinear sensor (ilqr_estimate_update_sensor): the
+        sensor is linearised on the device at the estimate and estimate_update_linear_'s update runs on the result; iterations > 1
+        (up to 8): the iterated filter, relinearised at each iteration's estimate and updated from the prior again. Returns the dict of
+        estimate_update_: xhat, P (new arrays), innovation [B, ny], nis [B], first_bad [B]."""
+        name, ny, per, s, r, _ = self._nl_sensor(sensor, s, r)
+        if r is None:
+            raise ValueError("r must be given")
+        xhat, P = self._estimate_arrays(xhat, P)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.shape != (self.B, ny):
+            raise ValueError("y must have shape [B, ny]")
+        out = dict(xhat=xhat, P=P, innovation=np.empty((self.B, ny)), nis=np.empty(self.B), first_bad=np.empty(self.B, dtype=np.int32))
+        _ffi.check(_ffi.lib().ilqr_estimate_update_sensor(self._h, name, per, _nul(s), int(iterations), _p(r), _p(y), _p(xhat), _p(P),
+                                                          _p(out["innovation"]), _p(out["nis"]), _i32p(out["first_bad"])))
+        return out
+
+    def estimate_update_sensor_device_(self, d_xhat_ptr, d_P_ptr, d_y_ptr, sensor, r, d_s_ptr=None, per_instance_s=False, iterations=1,
+                                       d_innovation_ptr=None, d_nis_ptr=None, d_first_bad_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not wanted), s among them; r stays a host array;
+        asynchronous on the handle's stream."""
+        _, ny, _ = sensor_dims(sensor)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(r, dtype=np.float64), (ny,)))
+        _ffi.check(_ffi.lib().ilqr_estimate_update_sensor_device(self._h, sensor.encode(), 1 if per_instance_s else 0, _vp(d_s_ptr), int(iterations),
+                                                                 _p(r), _vp(d_y_ptr), _vp(d_xhat_ptr), _vp(d_P_ptr), _vp(d_innovation_ptr),
+                                                                 _vp(d_nis_ptr), _vp(d_first_bad_ptr)))
+
     def _estimate_arrays(self, xhat, P):
         xhat, P = np.array(xhat, dtype=np.float64, order="C"), np.array(P, dtype=np.float64, order="C")
         if xhat.shape != (self.B, self.nx):
@@ -621,7 +730,10 @@ class Solver:
         The result carries xhat, pdiag, nis and the last covariance P; y_cl is then the measurement taken.
         estimator = dict(H=, r=, q=None, xhat0=None, P0=, sigma_y=None): the same loop with the linear sensor y = H x + v of
         plant_measure_linear_ / estimate_update_linear_ (ilqr_mpc_run_sensor), selected by the key H [ny, nx]; r and sigma_y have ny
-        entries, y_cl is [B, periods, ny]. Not together with `measured` or with the loop's own sigma_y."""
+        entries, y_cl is [B, periods, ny]. Not together with `measured` or with the loop's own sigma_y.
+        estimator = dict(sensor=, r=, s=None, q=None, xhat0=None, P0=, sigma_y=None, iterations=1): the same loop with a compiled
+        nonlinear sensor y = h(x, s) (compile_sensor; ilqr_mpc_run_nlsensor), selected by the key sensor: plant_measure_sensor_ and
+        estimate_update_sensor_ in the places of the linear ones; s [ns] or [B, ns]. Not together with H or `measured`."""
         periods = int(periods)
         if periods < 1:
             raise ValueError("periods must be >= 1")
@@ -630,18 +742,27 @@ class Solver:
         u_min, u_max = _limits(self.nu, u_min, u_max)
         sigma_y = _sigma_y(self.nx, sigma_y)
         io = u_min is not None or u_max is not None or sigma_y is not None or delay == 1
-        linear = estimator is not None and "H" in estimator
+        # the kind of estimator is named by one key: sensor (compiled nonlinear), H (linear), else the selection of state components
+        nonlinear = estimator is not None and "sensor" in estimator
+        linear = estimator is not None and not nonlinear and "H" in estimator
         if estimator is not None:
-            unknown = set(estimator) - ({"H", "q", "r", "xhat0", "P0", "sigma_y", "measured"} if linear else {"measured", "q", "r", "xhat0", "P0"})
-            if unknown:
-                raise ValueError("estimator: unknown keys %s" % sorted(unknown))
+            common = {"q", "r", "xhat0", "P0"}
+            allowed = common | ({"sensor", "s", "sigma_y", "iterations"} if nonlinear else {"H", "sigma_y"} if linear else {"measured"})
+            if nonlinear and ("H" in estimator or "measured" in estimator):
+                raise ValueError("estimator: sensor excludes H and measured")
             if linear and "measured" in estimator:
                 raise ValueError("estimator: H and measured exclude each other")
-            if linear and sigma_y is not None:
-                raise ValueError("estimator: with H the sensor's own sigma_y [ny] replaces the loop's")
+            unknown = set(estimator) - allowed
+            if unknown:
+                raise ValueError("estimator: unknown keys %s" % sorted(unknown))
+            if (linear or nonlinear) and sigma_y is not None:
+                raise ValueError("estimator: with a sensor (H or sensor) the sensor's own sigma_y [ny] replaces the loop's")
             if estimator.get("r") is None or estimator.get("P0") is None:
                 raise ValueError("estimator needs r and P0")
-            if linear:
+            if nonlinear:
+                e_name, e_ny, e_per, e_s, e_r, e_sigma = self._nl_sensor(estimator["sensor"], estimator.get("s"), estimator["r"], estimator.get("sigma_y"))
+                _, e_q, _ = _variances(self.nx, None, estimator.get("q"), None)
+            elif linear:
                 e_H, e_ny, e_r, e_sigma = self._sensor(estimator["H"], estimator["r"], estimator.get("sigma_y"), per_instance=False)
                 _, e_q, _ = _variances(self.nx, None, estimator.get("q"), None)
             else:
@@ -679,12 +800,15 @@ class Solver:
         out, scores = (_p(x), _p(u), _p(log), _i32p(nf)), (_nul(cl_cost), _nul(cl_violation))
         if estimator is not None or io:
             pio = _ffi.PlantIO(_nul(u_min), _nul(u_max), _nul(sigma_y), int(delay), 0)
-            y_cl, saturated = np.empty((self.B, periods, e_ny if linear else self.nx)), np.empty(self.B, dtype=np.int32)
+            y_cl, saturated = np.empty((self.B, periods, e_ny if (linear or nonlinear) else self.nx)), np.empty(self.B, dtype=np.int32)
             seam = (_p(y_cl), _i32p(saturated))
         # the plainest entry point that offers what was asked for, and its arguments behind the handle and the descriptor
         if estimator is not None:
             xhat, pdiag, nis = np.empty((self.B, periods, self.nx)), np.empty((self.B, periods, self.nx)), np.empty((self.B, periods))
-            if linear:
+            if nonlinear:
+                run, est = _ffi.lib().ilqr_mpc_run_nlsensor, _ffi.NlSensor(e_name, e_per, _nul(e_s), _p(e_r), _nul(e_q), _nul(e_sigma),
+                                                                             int(estimator.get("iterations", 1)))
+            elif linear:
                 run, est = _ffi.lib().ilqr_mpc_run_sensor, _ffi.Sensor(e_ny, 0, _p(e_H), _p(e_r), _nul(e_q), _nul(e_sigma))
             else:
                 run, est = _ffi.lib().ilqr_mpc_run_est, _ffi.Estimator(_i32p(e_measured), _nul(e_q), _p(e_r))

@@ -941,3 +941,47 @@ def c_constraint(prefix, k, terminal=False):
     if not terminal:
         src += c_callable(prefix + "_jacobian_action", _colmajor(k.jacobian_action), k)
     return src
+
+
+# --------------------------------------------------------------------------- a nonlinear sensor as C source (ilqr_compile_sensor)
+class _SensorPrinter(C99CodePrinter):
+    """plain C (math.h): small integer powers as products, nothing that depends on the device headers"""
+    def _print_Pow(self, expr):
+        b, e = expr.base, expr.exp
+        if e.is_Integer and 2 <= abs(int(e)) <= 4:
+            prod = "(" + "*".join([self.parenthesize(b, PRECEDENCE["Mul"])] * abs(int(e))) + ")"
+            return prod if int(e) > 0 else "(1.0/%s)" % prod
+        return super()._print_Pow(expr)
+
+
+def sensor_expressions(h, nx, ns):
+    """h(x, s) traced on symbols -> (x symbols, s symbols, rows [ny], Jacobian [ny][nx])"""
+    x, s = _variables("x", nx), _variables("s", ns)
+    rows = _as_list(h(x, s))
+    return x, s, rows, _jac(rows, x)
+
+
+def generate_sensor_source(name, h, nx, ns):
+    """The C source ilqr_compile_sensor takes, from a user function h(x, s) on symbols (x: nx states, s: ns sensor parameters, returns
+    the ny outputs): `ILQR_SENSOR_FN void sensor_row(int j, double* y, double* dydx, const double* x, const double* s)` as a
+    `switch (j)` with one case per row, each with its own common subexpressions, writing *y = h_j and only the structurally non-zero
+    partials dydx[k] = ∂h_j/∂x_k (dydx arrives zeroed). Returns (ny, source). `name` only labels the source."""
+    pr = _SensorPrinter({"strict": False})
+    x, s, rows, jac = sensor_expressions(h, nx, ns)
+    ny = len(rows)
+    if not (1 <= nx <= 64 and 1 <= ny <= 64 and 0 <= ns <= 64):
+        raise ValueError("a sensor has 1 <= nx <= 64, 1 <= ny <= 64 and 0 <= ns <= 64")
+    sub = {v: sp.Symbol("x[%d]" % i) for i, v in enumerate(x)}
+    sub.update({v: sp.Symbol("s[%d]" % i) for i, v in enumerate(s)})
+    out = ["// sensor %s: nx = %d, ny = %d, ns = %d" % (name, nx, ny, ns),
+           "ILQR_SENSOR_FN void sensor_row(int j, double* y, double* dydx, const double* x, const double* s) {", "    switch (j) {"]
+    for j in range(ny):
+        exprs = [rows[j]] + [sp.simplify(d) if d.has(sp.Derivative) else d for d in jac[j]]
+        repl, red = sp.cse(exprs, symbols=sp.numbered_symbols("t%d_" % j))
+        out.append("        case %d: {" % j)
+        out += ["            const double %s = %s;" % (sym, pr.doprint(e.xreplace(sub))) for sym, e in repl]
+        out.append("            *y = %s;" % pr.doprint(red[0].xreplace(sub)))
+        out += ["            dydx[%d] = %s;" % (k, pr.doprint(e.xreplace(sub))) for k, e in enumerate(red[1:]) if e != 0]
+        out.append("        } break;")
+    out += ["        default: break;", "    }", "}", ""]
+    return ny, "\n".join(out)

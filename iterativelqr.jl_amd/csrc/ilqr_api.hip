@@ -75,6 +75,16 @@ std::vector<const ilqr_model_vtable*>& registry() {
     static std::vector<const ilqr_model_vtable*> r;
     return r;
 }
+// compiled nonlinear sensors (ilqr_compile_sensor): a registry of their own, a sensor belongs to no model
+std::vector<const ilqr_sensor_vtable*>& sensor_registry() {
+    static std::vector<const ilqr_sensor_vtable*> r;
+    return r;
+}
+const ilqr_sensor_vtable* find_sensor(const char* name) {
+    for (auto* sv : sensor_registry())
+        if (name && !std::strcmp(sv->name, name)) return sv;
+    return nullptr;
+}
 
 struct BufferDesc { const char* name; int offset; int len; };
 
@@ -91,6 +101,8 @@ const ilqr_model_vtable* ilqr::find_model(const char* name) {
     return nullptr;
 }
 long long ilqr::model_abi_word() { return ILQR_MODEL_ABI_VERSION * 1000 + (long long)sizeof(ilqr::KArgs); }
+bool ilqr::sensor_registered(const char* name) { return find_sensor(name) != nullptr; }
+long long ilqr::sensor_abi_word() { return ILQR_SENSOR_ABI_VERSION * 1000 + (long long)sizeof(ilqr::SensorNlArgs); }
 using ilqr::fail;
 using ilqr::find_model;
 
@@ -100,7 +112,8 @@ enum { CAND_U, CAND_COST, CAND_VIOL, CAND_NONFINITE, CAND_CHOSEN, CAND_STAGES };
 enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
 enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_SATURATED, PLANT_XC,
-       PLANT_Y, EST_P, EST_Y, EST_INNOVATION, EST_NIS, EST_FIRST_BAD, EST_XHAT_CL, EST_PDIAG_CL, EST_NIS_CL, SENS_H, SENS_R, SENS_SIGMA, SENS_YHAT, PLANT_STAGES };
+       PLANT_Y, EST_P, EST_Y, EST_INNOVATION, EST_NIS, EST_FIRST_BAD, EST_XHAT_CL, EST_PDIAG_CL, EST_NIS_CL, SENS_H, SENS_R, SENS_SIGMA, SENS_YHAT, SENS_S,
+       SENS_XLIN, SENS_XPRIOR, SENS_X0, SENS_P0, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -169,7 +182,9 @@ struct ilqr_handle {
     // given per period (y_cl, in the stage of y) and the saturation counts of the run; ilqr_estimate_predict / _update: the estimate in
     // the stage of xc, y in its own, the covariance, the innovation, nis and first_bad; ilqr_mpc_run_est: the covariance, the period's
     // measurement and nis, and the three per-period logs of the filter; ilqr_estimate_update_linear / ilqr_plant_measure_linear /
-    // ilqr_mpc_run_sensor: H, r, sigma_y and ŷ
+    // ilqr_mpc_run_sensor: H, r, sigma_y and ŷ; ilqr_sensor_linearise / ilqr_plant_measure_sensor / ilqr_estimate_update_sensor /
+    // ilqr_mpc_run_nlsensor: the sensor parameters s, the point of linearisation and the prior of its host form, the Jacobians H
+    // [B][ny][nx] and ŷ the update reads (in the stages of H and ŷ), and the prior (x̂₀, P₀) of the iterated filter
     Stage plant[PLANT_STAGES];
 };
 
@@ -574,6 +589,32 @@ int ilqr_register_model(const ilqr_model_vtable* vt) {
     return ILQR_OK;
 }
 int ilqr_model_count(void) { return (int)registry().size(); }
+
+int ilqr_register_sensor(const void* vtable) {
+    const ilqr_sensor_vtable* sv = (const ilqr_sensor_vtable*)vtable;
+    if (!sv) return ILQR_ERR_INVALID;
+    // a module built against other headers would be handed a SensorNlArgs it misreads: refuse it
+    if (sv->abi_version != ILQR_SENSOR_ABI_VERSION || sv->args_bytes != (int)sizeof(ilqr::SensorNlArgs))
+        return fail(ILQR_ERR_MODEL, "sensor module was built against a different library version (ABI mismatch): rebuild it");
+    if (!sv->name) return ILQR_ERR_INVALID;
+    auto& r = sensor_registry();
+    for (auto& e : r)
+        if (!std::strcmp(e->name, sv->name)) { e = sv; return ILQR_OK; }
+    r.push_back(sv);
+    return ILQR_OK;
+}
+int ilqr_sensor_count(void) { return (int)sensor_registry().size(); }
+const char* ilqr_sensor_name(int32_t i) {
+    return (i >= 0 && i < (int)sensor_registry().size()) ? sensor_registry()[i]->name : nullptr;
+}
+int ilqr_sensor_dims(const char* sensor, int32_t* nx, int32_t* ny, int32_t* ns) {
+    const ilqr_sensor_vtable* sv = find_sensor(sensor);
+    if (!sv) return fail(ILQR_ERR_INVALID, "ilqr_sensor_dims: unknown sensor");
+    if (nx) *nx = sv->nx;
+    if (ny) *ny = sv->ny;
+    if (ns) *ns = sv->ns;
+    return ILQR_OK;
+}
 
 const char* ilqr_model_name(int32_t i) {
     return (i >= 0 && i < (int)registry().size()) ? registry()[i]->name : nullptr;
@@ -1766,13 +1807,184 @@ int ilqr_plant_measure_linear(ilqr_handle* h, uint64_t seed, int64_t first_insta
                           return measure_linear_launch(s, seed, first_instance + (int64_t)lo, step, ny, a[0].d(), a[1].d(), a[2].d(), a[3].d()); });
 }
 
+// ---- a nonlinear sensor y = h(x, s) + v compiled as a module of its own (ilqr_device_sensor_nl.hpp, ilqr_compile_sensor)
+// everything that can be refused without touching the GPU; what needs no handle comes first. s_host: s is a host array (its entries
+// are looked at); r, sigma_y: null where the call takes none; iterations: 1 where the call takes none
+static int nl_sensor_args_check(const char* sensor, int32_t per_instance_s, const double* s, int32_t iterations, const double* r,
+                                const double* sigma_y, const ilqr_sensor_vtable** out, const char* who) {
+    const std::string me(who);
+    if (!sensor) return fail(ILQR_ERR_INVALID, me + ": null sensor name");
+    const ilqr_sensor_vtable* sv = find_sensor(sensor);
+    if (!sv) return fail(ILQR_ERR_INVALID, me + ": unknown sensor '" + sensor + "' (ilqr_compile_sensor / ilqr_load_sensor_library register one)");
+    if (per_instance_s != 0 && per_instance_s != 1) return fail(ILQR_ERR_INVALID, me + ": per_instance_s must be 0 or 1");
+    if (iterations < 1 || iterations > ilqr::SENSOR_NL_MAX_ITERATIONS) return fail(ILQR_ERR_INVALID, me + ": iterations must lie in 1 .. 8");
+    if (sv->ns > 0 && !s) return fail(ILQR_ERR_INVALID, me + ": null s for a sensor with parameters");
+    for (int j = 0; r && j < sv->ny; ++j)
+        if (!(r[j] > 0.0) || !std::isfinite(r[j])) return fail(ILQR_ERR_INVALID, me + ": r must be finite and > 0");
+    ILQR_TRY(sigma_check(sigma_y, sv->ny, me, "sigma_y"));
+    *out = sv;
+    return ILQR_OK;
+}
+// what needs the handle: its nx, and with it the extent of a host s
+static int nl_sensor_handle_check(const ilqr_handle* h, const ilqr_sensor_vtable* sv, int32_t per_instance_s, const double* s, bool s_host,
+                                  const char* who) {
+    const std::string me(who);
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (sv->nx != h->L.nx) return fail(ILQR_ERR_INVALID, me + ": the sensor's nx is not the handle's");
+    if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
+    const size_t count = (per_instance_s ? (size_t)h->B : 1) * (size_t)sv->ns;
+    for (size_t e = 0; s && s_host && e < count; ++e)
+        if (!std::isfinite(s[e])) return fail(ILQR_ERR_INVALID, me + ": a non-finite entry of s");
+    return ILQR_OK;
+}
+static int nl_sensor_check(const ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, bool s_host, int32_t iterations,
+                           const double* r, const double* sigma_y, const ilqr_sensor_vtable** out, const char* who) {
+    ILQR_TRY(nl_sensor_args_check(sensor, per_instance_s, s, iterations, r, sigma_y, out, who));
+    return nl_sensor_handle_check(h, *out, per_instance_s, s, s_host, who);
+}
+
+// the sensor parameters of a host form: one row per instance, or the one copy the batch reads
+static Staged staged_s(const ilqr_sensor_vtable* sv, int32_t per_instance_s, const double* s) {
+    return per_instance_s ? staged_in(IN_PLANT, SENS_S, s, (size_t)sv->ns) : staged_shared(IN_PLANT, SENS_S, s, (size_t)sv->ns);
+}
+
+// every pointer a device pointer on h's device (s: or null where ns == 0; x_prior: or null)
+static int nl_linearise_launch(ilqr_handle* h, const ilqr_sensor_vtable* sv, int32_t per_instance_s, const double* s, const double* x_lin,
+                               const double* x_prior, double* H, double* yhat) {
+    ilqr::SensorNlArgs a = {};
+    a.B = h->B; a.s_stride = per_instance_s ? sv->ns : 0; a.s = s; a.x = x_lin; a.x_prior = x_prior; a.H = H; a.yhat = yhat;
+    if (sv->launch_linearise(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "sensor linearisation launch failed");
+    return ILQR_OK;
+}
+
+// sigma_y (or null), x, y: device pointers on h's device
+static int nl_measure_launch(ilqr_handle* h, const ilqr_sensor_vtable* sv, int32_t per_instance_s, const double* s, uint64_t seed,
+                             int64_t first_instance, int32_t step, const double* sigma_y, const double* x, double* y) {
+    ilqr::SensorNlArgs a = {};
+    a.B = h->B; a.s_stride = per_instance_s ? sv->ns : 0; a.s = s; a.x = x; a.y_out = y; a.sigma = sigma_y; a.step = step; a.seed = seed;
+    a.b0 = first_instance;
+    if (sv->launch_measure(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "sensor measurement launch failed");
+    return ILQR_OK;
+}
+
+// The update of `iterations` iterations: every pointer a device pointer on h's device. Hb [B][ny][nx] and yh [B][ny] are the buffers
+// the linearisation writes and the existing update reads; x0 [B][nx] and P0 [B][nx][nx] keep the prior of the iterated filter (not
+// touched where iterations == 1). Iteration i >= 1 linearises at the estimate iteration i−1 left BEFORE the prior is restored over it.
+static int nl_update_launch(ilqr_handle* h, const ilqr_sensor_vtable* sv, int32_t per_instance_s, const double* s, int32_t iterations,
+                            const double* r, const double* y, double* xhat, double* P, double* innovation, double* nis, int32_t* first_bad,
+                            double* Hb, double* yh, double* x0, double* P0) {
+    const size_t xb = (size_t)h->B * (size_t)h->L.nx * 8, pb = xb * (size_t)h->L.nx;
+    if (iterations > 1) {
+        HIP_TRY(hipMemcpyAsync(x0, xhat, xb, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(P0, P, pb, hipMemcpyDeviceToDevice, h->stream));
+    }
+    for (int32_t i = 0; i < iterations; ++i) {
+        ILQR_TRY(nl_linearise_launch(h, sv, per_instance_s, s, xhat, i ? x0 : nullptr, Hb, yh));
+        if (i) {
+            HIP_TRY(hipMemcpyAsync(xhat, x0, xb, hipMemcpyDeviceToDevice, h->stream));
+            HIP_TRY(hipMemcpyAsync(P, P0, pb, hipMemcpyDeviceToDevice, h->stream));
+        }
+        ILQR_TRY(sensor_update_launch(h, sv->ny, 1, Hb, r, y, yh, xhat, P, innovation, nis, first_bad));
+    }
+    return ILQR_OK;
+}
+
+int ilqr_sensor_linearise_device(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, const double* x_lin,
+                                 const double* x_prior, double* H_out, double* yhat_out) {
+    if (!x_lin || !H_out || !yhat_out) return fail(ILQR_ERR_INVALID, "ilqr_sensor_linearise_device: null x_lin, H_out or yhat_out");
+    const ilqr_sensor_vtable* sv = nullptr;
+    ILQR_TRY(nl_sensor_check(h, sensor, per_instance_s, s, false, 1, nullptr, nullptr, &sv, "ilqr_sensor_linearise_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_sensor_linearise");
+    HIP_TRY(hipSetDevice(h->device));
+    return nl_linearise_launch(h, sv, per_instance_s, s, x_lin, x_prior, H_out, yhat_out);
+}
+
+int ilqr_sensor_linearise(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, const double* x_lin, const double* x_prior,
+                          double* H_out, double* yhat_out) {
+    if (!x_lin || !H_out || !yhat_out) return fail(ILQR_ERR_INVALID, "ilqr_sensor_linearise: null x_lin, H_out or yhat_out");
+    const ilqr_sensor_vtable* sv = nullptr;
+    ILQR_TRY(nl_sensor_check(h, sensor, per_instance_s, s, true, 1, nullptr, nullptr, &sv, "ilqr_sensor_linearise"));
+    const size_t n = (size_t)h->L.nx, m = (size_t)sv->ny;
+    return run_staged(h, {staged_s(sv, per_instance_s, s), staged_in(IN_PLANT, SENS_XLIN, x_lin, n), staged_in(IN_PLANT, SENS_XPRIOR, x_prior, n),
+                          staged_out(IN_PLANT, SENS_H, H_out, m * n), staged_out(IN_PLANT, SENS_YHAT, yhat_out, m)},
+                      [&](ilqr_handle* sh, size_t, const Staged* a) {
+                          return nl_linearise_launch(sh, sv, per_instance_s, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].d()); });
+}
+
+int ilqr_plant_measure_sensor_device(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, uint64_t seed,
+                                     int64_t first_instance, int32_t step, const double* sigma_y, const double* x, double* y) {
+    if (!x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_sensor_device: null x or y");
+    const ilqr_sensor_vtable* sv = nullptr;
+    ILQR_TRY(nl_sensor_args_check(sensor, per_instance_s, s, 1, nullptr, sigma_y, &sv, "ilqr_plant_measure_sensor_device"));
+    ILQR_TRY(measure_check(h, first_instance, step, nullptr, "ilqr_plant_measure_sensor_device"));
+    ILQR_TRY(nl_sensor_handle_check(h, sv, per_instance_s, s, false, "ilqr_plant_measure_sensor_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_plant_measure_sensor");
+    HIP_TRY(hipSetDevice(h->device));
+    if (sigma_y) ILQR_TRY(sensor_vector_upload(h, h->plant[SENS_SIGMA], sigma_y, sv->ny));
+    return nl_measure_launch(h, sv, per_instance_s, s, seed, first_instance, step, sigma_y ? (const double*)h->plant[SENS_SIGMA].p : nullptr, x, y);
+}
+
+int ilqr_plant_measure_sensor(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, uint64_t seed, int64_t first_instance,
+                              int32_t step, const double* sigma_y, const double* x, double* y) {
+    if (!x || !y) return fail(ILQR_ERR_INVALID, "ilqr_plant_measure_sensor: null x or y");
+    const ilqr_sensor_vtable* sv = nullptr;
+    ILQR_TRY(nl_sensor_args_check(sensor, per_instance_s, s, 1, nullptr, sigma_y, &sv, "ilqr_plant_measure_sensor"));
+    ILQR_TRY(measure_check(h, first_instance, step, nullptr, "ilqr_plant_measure_sensor"));
+    ILQR_TRY(nl_sensor_handle_check(h, sv, per_instance_s, s, true, "ilqr_plant_measure_sensor"));
+    const size_t n = (size_t)h->L.nx, m = (size_t)sv->ny;
+    return run_staged(h, {staged_s(sv, per_instance_s, s), staged_shared(IN_PLANT, SENS_SIGMA, sigma_y, m), staged_in(IN_PLANT, PLANT_X, x, n),
+                          staged_out(IN_PLANT, PLANT_Y, y, m)},
+                      [&](ilqr_handle* sh, size_t lo, const Staged* a) {
+                          return nl_measure_launch(sh, sv, per_instance_s, a[0].d(), seed, first_instance + (int64_t)lo, step, a[1].d(), a[2].d(), a[3].d()); });
+}
+
+int ilqr_estimate_update_sensor_device(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, int32_t iterations,
+                                       const double* r, const double* y, double* xhat, double* P, double* innovation, double* nis,
+                                       int32_t* first_bad) {
+    if (!r || !y || !xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update_sensor_device: null r, y, xhat or P");
+    const ilqr_sensor_vtable* sv = nullptr;
+    ILQR_TRY(nl_sensor_check(h, sensor, per_instance_s, s, false, iterations, r, nullptr, &sv, "ilqr_estimate_update_sensor_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_estimate_update_sensor");
+    HIP_TRY(hipSetDevice(h->device));
+    // the handle's buffers, reused by later calls: they grow (and then wait for the stream) only when a call needs more than any before it
+    const size_t B = (size_t)h->B, n = (size_t)h->L.nx, m = (size_t)sv->ny;
+    ILQR_TRY(grow(h, h->plant[SENS_H], B * m * n * 8));
+    ILQR_TRY(grow(h, h->plant[SENS_YHAT], B * m * 8));
+    if (iterations > 1) {
+        ILQR_TRY(grow(h, h->plant[SENS_X0], B * n * 8));
+        ILQR_TRY(grow(h, h->plant[SENS_P0], B * n * n * 8));
+    }
+    ILQR_TRY(sensor_vector_upload(h, h->plant[SENS_R], r, sv->ny));
+    return nl_update_launch(h, sv, per_instance_s, s, iterations, (const double*)h->plant[SENS_R].p, y, xhat, P, innovation, nis, first_bad,
+                            (double*)h->plant[SENS_H].p, (double*)h->plant[SENS_YHAT].p, (double*)h->plant[SENS_X0].p, (double*)h->plant[SENS_P0].p);
+}
+
+int ilqr_estimate_update_sensor(ilqr_handle* h, const char* sensor, int32_t per_instance_s, const double* s, int32_t iterations, const double* r,
+                                const double* y, double* xhat, double* P, double* innovation, double* nis, int32_t* first_bad) {
+    if (!r || !y || !xhat || !P) return fail(ILQR_ERR_INVALID, "ilqr_estimate_update_sensor: null r, y, xhat or P");
+    const ilqr_sensor_vtable* sv = nullptr;
+    ILQR_TRY(nl_sensor_check(h, sensor, per_instance_s, s, true, iterations, r, nullptr, &sv, "ilqr_estimate_update_sensor"));
+    const size_t n = (size_t)h->L.nx, m = (size_t)sv->ny;
+    const bool it = iterations > 1;
+    // the estimate and its covariance go in and come back; H, ŷ and the prior stay on the device
+    return run_staged(h, {staged_s(sv, per_instance_s, s), staged_shared(IN_PLANT, SENS_R, r, m), staged_in(IN_PLANT, EST_Y, y, m),
+                          staged_io(IN_PLANT, PLANT_XC, xhat, n), staged_io(IN_PLANT, EST_P, P, n * n), staged_out(IN_PLANT, EST_INNOVATION, innovation, m),
+                          staged_out(IN_PLANT, EST_NIS, nis, 1), staged_out(IN_PLANT, EST_FIRST_BAD, first_bad, 1),
+                          staged_device(IN_PLANT, SENS_H, true, m * n), staged_device(IN_PLANT, SENS_YHAT, true, m),
+                          staged_device(IN_PLANT, SENS_X0, it, n), staged_device(IN_PLANT, SENS_P0, it, n * n)},
+                      [&](ilqr_handle* sh, size_t, const Staged* a) {
+                          return nl_update_launch(sh, sv, per_instance_s, a[0].d(), iterations, a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].d(), a[6].d(),
+                                                  a[7].i(), a[8].d(), a[9].d(), a[10].d(), a[11].d()); });
+}
+
 // ---- the closed MPC loop, enqueued once: per period plant step, score, horizon shift, dual shift, solve, log row
 static_assert(ILQR_MPC_LOG_W == ilqr::MPC_LOG_W, "the log row of the header is the kernel's");
 // One run of the loop as an entry point hands it over: the descriptor, the seam (io), the filter (est: the extended Kalman filter, or
-// sens: the linear sensor in its place), every input and output array of the batch, and the entry point's name. What an entry point
-// does not offer stays null.
+// sens: the linear sensor in its place, or nls: the compiled nonlinear one, with nlv its module once the check has found it), every
+// input and output array of the batch, and the entry point's name. What an entry point does not offer stays null.
 struct MpcRun {
-    const ilqr_mpc_desc* d; const ilqr_plant_io* io; const ilqr_estimator* est; const ilqr_sensor* sens;
+    const ilqr_mpc_desc* d; const ilqr_plant_io* io; const ilqr_estimator* est; const ilqr_sensor* sens; const ilqr_nl_sensor* nls;
+    const ilqr_sensor_vtable* nlv;
     const double *x0, *xhat0, *w_plant, *w_preview;
     double *Pcov, *x_cl, *u_cl, *log, *cl_cost, *cl_violation, *y_cl, *xhat_cl, *pdiag_cl, *nis_cl;
     int32_t *first_nonfinite, *saturated;
@@ -1781,7 +1993,7 @@ struct MpcRun {
 // The seam between plant and controller is in use: limits, measurement noise, a delay, a filter, or one of the two outputs that report
 // on it. Otherwise the loop hands the shift the plant state itself: no launch, no buffer and no argument of it differs from ilqr_mpc_run's.
 static bool mpc_measured(const MpcRun& r) {
-    return (r.io && (r.io->u_min || r.io->u_max || r.io->sigma_y || r.io->delay)) || r.y_cl || r.saturated || r.est || r.sens;
+    return (r.io && (r.io->u_min || r.io->u_max || r.io->sigma_y || r.io->delay)) || r.y_cl || r.saturated || r.est || r.sens || r.nls;
 }
 // everything its constituents refuse for these arguments, before any launch
 // measured: the run goes through the measurement slot (mpc_measured)
@@ -1800,7 +2012,16 @@ static int mpc_check(const ilqr_handle* h, const MpcRun& r, bool measured) {
             if (!(sens->r[j] > 0.0) || !std::isfinite(sens->r[j])) return fail(ILQR_ERR_INVALID, me + ": r must be finite and > 0");
         ILQR_TRY(sigma_check(sens->sigma_y, sens->ny, me, "sigma_y"));
     }
-    if (!est && !sens && (r.xhat0 || r.Pcov || r.xhat_cl || r.pdiag_cl || r.nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
+    const ilqr_nl_sensor* nls = r.nls;
+    if (nls) {                                     // the compiled sensor in the estimator's place; what needs no handle, as its calls order it
+        if (!r.Pcov) return fail(ILQR_ERR_INVALID, me + ": a sensor with a null P");
+        if (io && io->sigma_y) return fail(ILQR_ERR_INVALID, me + ": io->sigma_y together with a sensor: the sensor's own sigma_y [ny] replaces it");
+        if (!nls->r) return fail(ILQR_ERR_INVALID, me + ": null r");
+        const ilqr_sensor_vtable* sv = nullptr;
+        ILQR_TRY(nl_sensor_args_check(nls->sensor, nls->ns_per_instance, nls->s, nls->iterations, nls->r, nls->sigma_y, &sv, who));
+        ILQR_TRY(variance_check(nullptr, nls->q, nullptr, 1, me));
+    }
+    if (!est && !sens && !nls && (r.xhat0 || r.Pcov || r.xhat_cl || r.pdiag_cl || r.nis_cl)) return fail(ILQR_ERR_INVALID, me + ": xhat0, P, xhat_cl, pdiag_cl or nis_cl without an estimator");
     if (est && !r.Pcov) return fail(ILQR_ERR_INVALID, me + ": an estimator with a null P");
     if (est) {                                     // what needs no handle, as the two estimator calls order it
         if (!est->r) return fail(ILQR_ERR_INVALID, me + ": null r");
@@ -1830,20 +2051,27 @@ static int mpc_check(const ilqr_handle* h, const MpcRun& r, bool measured) {
         ILQR_TRY(variance_check(nullptr, sens->q, nullptr, h->L.nx, me));
         ILQR_TRY(sensor_check(h, sens->ny, 0, sens->H, sens->r, sens->sigma_y, who));
     }
+    if (nls) {
+        const ilqr_sensor_vtable* sv = nullptr;
+        ILQR_TRY(variance_check(nullptr, nls->q, nullptr, h->L.nx, me));
+        ILQR_TRY(nl_sensor_check(h, nls->sensor, nls->ns_per_instance, nls->s, true, nls->iterations, nls->r, nls->sigma_y, &sv, who));
+    }
     return ILQR_OK;
 }
 
 // the arrays of a run (mpc_arrays) by name
 enum { M_X, M_W, M_PREVIEW, M_X_CL, M_U_CL, M_LOG, M_NONFINITE, M_COST, M_VIOL, M_Y_CL, M_SATURATED, M_XC, M_P, M_XHAT_CL, M_PDIAG_CL, M_NIS_CL, M_SENS_H,
-       M_SENS_R, M_SENS_SIGMA, M_YM, M_NIS, M_W_STAGE, M_RESIDENT };
+       M_SENS_R, M_SENS_SIGMA, M_YM, M_NIS, M_W_STAGE, M_RESIDENT, M_NL_S, M_NL_H, M_NL_YHAT, M_NL_X0, M_NL_P0 };
 
 // Every buffer of the run exists before its first launch — the plant state also without an x0, the closed-loop trajectory the score
 // reads even when the caller does not ask for it, the controller's state of a measured run, the period's measurement and nis of a
 // filter, what the shift would allocate in its first call and the resident inputs — so that nothing between the first plant launch
-// and the synchronise at the end waits for the device. The sensor's H, r and sigma_y are copied once, before the first launch.
+// and the synchronise at the end waits for the device. The sensor's H, r and sigma_y are copied once, before the first launch; so are
+// the compiled sensor's s, r and sigma_y, whose Jacobians, ŷ and (iterated) prior get their buffers here too.
 static std::vector<Staged> mpc_arrays(const ilqr_handle* h, const MpcRun& r, bool measured) {
-    const bool filt = r.est || r.sens, score = r.cl_cost != nullptr;
-    const size_t ym_n = r.sens ? (size_t)r.sens->ny : (size_t)h->L.nx;       // the numbers of one measurement
+    const bool filt = r.est || r.sens || r.nls, score = r.cl_cost != nullptr, iterated = r.nls && r.nls->iterations > 1;
+    const size_t ym_n = r.sens ? (size_t)r.sens->ny : (r.nls ? (size_t)r.nlv->ny : (size_t)h->L.nx);       // the numbers of one measurement
+    const size_t nl_ns = r.nls ? (size_t)r.nlv->ns : 0;
     const size_t P = (size_t)r.d->periods, R = P * (size_t)r.d->steps, n = (size_t)h->L.nx, m = (size_t)h->L.nu, nwu = (size_t)(h->L.nw - h->n_sel);
     return {staged_in(IN_PLANT, PLANT_X, r.x0, n).kept(true), staged_in(IN_PLANT, PLANT_W, r.w_plant, R * nwu), staged_in(IN_PLANT, PLANT_W_PREVIEW, r.w_preview, R * nwu),
             staged_out(IN_PLANT, PLANT_X_OUT, r.x_cl, (R + 1) * n).kept(score), staged_out(IN_PLANT, PLANT_U_OUT, r.u_cl, R * m).kept(score),
@@ -1852,10 +2080,13 @@ static std::vector<Staged> mpc_arrays(const ilqr_handle* h, const MpcRun& r, boo
             staged_out(IN_PLANT, PLANT_Y, r.y_cl, P * ym_n), staged_out(IN_PLANT, PLANT_SATURATED, r.saturated, 1),
             staged_in(IN_PLANT, PLANT_XC, r.xhat0, n).kept(measured), staged_io(IN_PLANT, EST_P, r.Pcov, n * n),      // P0 in, the last covariance back
             staged_out(IN_PLANT, EST_XHAT_CL, r.xhat_cl, P * n), staged_out(IN_PLANT, EST_PDIAG_CL, r.pdiag_cl, P * n), staged_out(IN_PLANT, EST_NIS_CL, r.nis_cl, P),
-            staged_shared(IN_PLANT, SENS_H, r.sens ? r.sens->H : nullptr, ym_n * n), staged_shared(IN_PLANT, SENS_R, r.sens ? r.sens->r : nullptr, ym_n),
-            staged_shared(IN_PLANT, SENS_SIGMA, r.sens ? r.sens->sigma_y : nullptr, ym_n),
+            staged_shared(IN_PLANT, SENS_H, r.sens ? r.sens->H : nullptr, ym_n * n), staged_shared(IN_PLANT, SENS_R, r.sens ? r.sens->r : (r.nls ? r.nls->r : nullptr), ym_n),
+            staged_shared(IN_PLANT, SENS_SIGMA, r.sens ? r.sens->sigma_y : (r.nls ? r.nls->sigma_y : nullptr), ym_n),
             staged_device(IN_PLANT, EST_Y, filt, ym_n), staged_device(IN_PLANT, EST_NIS, filt, 1),
-            staged_device(IN_SHIFT, SHIFT_W_STAGE, h->L.nw > 0, (size_t)h->L.T * (size_t)h->L.nw), staged_device(IN_RESIDENT, 0, true, n)};
+            staged_device(IN_SHIFT, SHIFT_W_STAGE, h->L.nw > 0, (size_t)h->L.T * (size_t)h->L.nw), staged_device(IN_RESIDENT, 0, true, n),
+            r.nls && r.nls->ns_per_instance ? staged_in(IN_PLANT, SENS_S, r.nls->s, nl_ns) : staged_shared(IN_PLANT, SENS_S, r.nls ? r.nls->s : nullptr, nl_ns),
+            staged_device(IN_PLANT, SENS_H, r.nls != nullptr && !r.sens, ym_n * n), staged_device(IN_PLANT, SENS_YHAT, r.nls != nullptr, ym_n),
+            staged_device(IN_PLANT, SENS_X0, iterated, n), staged_device(IN_PLANT, SENS_P0, iterated, n * n)};
 }
 
 // A run on one handle while it is enqueued: its arrays on the device, the plant state xp, the controller's view of it xc (what the shift
@@ -1873,9 +2104,9 @@ struct MpcState {
 // everything before the first period
 static int mpc_begin(ilqr_handle* h, const MpcRun& r, MpcState& st) {
     const Staged* a = st.a;
-    st.filt = r.est || r.sens; st.delayed = r.io && r.io->delay == 1; st.score = r.cl_cost != nullptr;
+    st.filt = r.est || r.sens || r.nls; st.delayed = r.io && r.io->delay == 1; st.score = r.cl_cost != nullptr;
     st.u_min = r.io ? r.io->u_min : nullptr; st.u_max = r.io ? r.io->u_max : nullptr; st.sigma_y = r.io ? r.io->sigma_y : nullptr;
-    st.rows = (long long)r.d->periods * r.d->steps; st.ym_n = r.sens ? (size_t)r.sens->ny : (size_t)h->L.nx;
+    st.rows = (long long)r.d->periods * r.d->steps; st.ym_n = r.sens ? (size_t)r.sens->ny : (r.nls ? (size_t)r.nlv->ny : (size_t)h->L.nx);
     st.xp = a[M_X].d();
     st.xc = st.measured ? a[M_XC].d() : st.xp;
     st.d_x_cl = a[M_X_CL].d(); st.d_u_cl = a[M_U_CL].d();
@@ -1890,18 +2121,21 @@ static int mpc_begin(ilqr_handle* h, const MpcRun& r, MpcState& st) {
 }
 
 // the measurement at plant step `step`, the update with it and the estimate's move to the end of the period under the plan in
-// flight: the selection of state components, or the linear sensor
+// flight: the selection of state components, the linear sensor, or the compiled nonlinear one
 static int mpc_measure(ilqr_handle* h, const MpcRun& r, const MpcState& st, int32_t step) {
     const ilqr_mpc_desc* d = r.d;
+    if (r.nls) return nl_measure_launch(h, r.nlv, r.nls->ns_per_instance, st.a[M_NL_S].d(), d->seed, d->first_instance, step, st.a[M_SENS_SIGMA].d(), st.xp, st.ym);
     return r.sens ? measure_linear_launch(h, d->seed, d->first_instance, step, r.sens->ny, st.a[M_SENS_H].d(), st.a[M_SENS_SIGMA].d(), st.xp, st.ym)
                   : measure_launch(h, d->seed, d->first_instance, step, st.sigma_y, st.xp, st.ym);
 }
 static int mpc_update(ilqr_handle* h, const MpcRun& r, const MpcState& st) {
+    if (r.nls) return nl_update_launch(h, r.nlv, r.nls->ns_per_instance, st.a[M_NL_S].d(), r.nls->iterations, st.a[M_SENS_R].d(), st.ym, st.xc, st.a[M_P].d(),
+                                       nullptr, st.d_nis, nullptr, st.a[M_NL_H].d(), st.a[M_NL_YHAT].d(), st.a[M_NL_X0].d(), st.a[M_NL_P0].d());
     return r.sens ? sensor_update_launch(h, r.sens->ny, 0, st.a[M_SENS_H].d(), st.a[M_SENS_R].d(), st.ym, nullptr, st.xc, st.a[M_P].d(), nullptr, st.d_nis, nullptr)
                   : update_launch(h, r.est->measured, r.est->r, st.ym, st.xc, st.a[M_P].d(), nullptr, st.d_nis, nullptr);
 }
 static int mpc_predict(ilqr_handle* h, const MpcRun& r, const MpcState& st) {
-    return predict_launch(h, r.d->steps, r.d->plant_feedback, st.u_min, st.u_max, r.est ? r.est->q : r.sens->q, st.xc, st.a[M_P].d());
+    return predict_launch(h, r.d->steps, r.d->plant_feedback, st.u_min, st.u_max, r.est ? r.est->q : (r.sens ? r.sens->q : r.nls->q), st.xc, st.a[M_P].d());
 }
 
 // the seam before the plant steps of period p: a delayed run only
@@ -2012,6 +2246,8 @@ static int mpc_run(ilqr_handle* h, const MpcRun& r) {
     if (r.est && (!h->vt->launch_estimate_predict || !h->vt->launch_estimate_update)) return fail(ILQR_ERR_MODEL, "this model module has no estimator kernel");
     if (r.sens && (!h->vt->launch_estimate_predict || !h->vt->launch_sensor_update || !h->vt->launch_plant_measure_linear))
         return fail(ILQR_ERR_MODEL, "this model module has no linear sensor kernel");
+    if (r.nls && (!h->vt->launch_estimate_predict || !h->vt->launch_sensor_update))
+        return fail(ILQR_ERR_MODEL, "this model module has no estimator or sensor update kernel for a nonlinear sensor to run on");
     return run_staged(h, mpc_arrays(h, r, measured),
                       [&](ilqr_handle* s, size_t lo, const Staged* arrays) { return mpc_enqueue(s, r, measured, lo, arrays); });
 }
@@ -2057,6 +2293,18 @@ int ilqr_mpc_run_sensor(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant
                         int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl,
                         double* pdiag_cl, double* nis_cl) {
     MpcRun r = {}; r.who = "ilqr_mpc_run_sensor"; r.d = d; r.io = io; r.sens = sensor;
+    r.x0 = x0; r.xhat0 = xhat0; r.Pcov = P; r.w_plant = w_plant; r.w_preview = w_preview;
+    r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite; r.cl_cost = cl_cost; r.cl_violation = cl_violation;
+    r.y_cl = y_cl; r.saturated = saturated; r.xhat_cl = xhat_cl; r.pdiag_cl = pdiag_cl; r.nis_cl = nis_cl;
+    return mpc_run(h, r);
+}
+
+int ilqr_mpc_run_nlsensor(ilqr_handle* h, const ilqr_mpc_desc* d, const ilqr_plant_io* io, const ilqr_nl_sensor* sensor, const double* x0,
+                          const double* xhat0, double* P, const double* w_plant, const double* w_preview, double* x_cl, double* u_cl, double* log,
+                          int32_t* first_nonfinite, double* cl_cost, double* cl_violation, double* y_cl, int32_t* saturated, double* xhat_cl,
+                          double* pdiag_cl, double* nis_cl) {
+    MpcRun r = {}; r.who = "ilqr_mpc_run_nlsensor"; r.d = d; r.io = io; r.nls = sensor;
+    r.nlv = sensor && sensor->sensor ? find_sensor(sensor->sensor) : nullptr;          // (an unknown name: mpc_check refuses it)
     r.x0 = x0; r.xhat0 = xhat0; r.Pcov = P; r.w_plant = w_plant; r.w_preview = w_preview;
     r.x_cl = x_cl; r.u_cl = u_cl; r.log = log; r.first_nonfinite = first_nonfinite; r.cl_cost = cl_cost; r.cl_violation = cl_violation;
     r.y_cl = y_cl; r.saturated = saturated; r.xhat_cl = xhat_cl; r.pdiag_cl = pdiag_cl; r.nis_cl = nis_cl;

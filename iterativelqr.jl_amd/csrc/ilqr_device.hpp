@@ -2333,6 +2333,7 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_score.hpp"
 #include "ilqr_device_estimate.hpp"
 #include "ilqr_device_sensor.hpp"
+#include "ilqr_device_sensor_nl.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.

@@ -15,6 +15,10 @@ ILQR_INTERNAL int fail(int code, const std::string& msg);                  // se
 ILQR_INTERNAL const ilqr_model_vtable* find_model(const char* name);       // the registered module of that name, or nullptr
 // eighth word of a model module's hash: ILQR_MODEL_ABI_VERSION * 1000 + sizeof(KArgs)
 ILQR_INTERNAL long long model_abi_word();
+// the sensor registry's side of the same (ilqr_compile_sensor): a registered sensor module's presence, and the word of its hash,
+// ILQR_SENSOR_ABI_VERSION * 1000 + sizeof(SensorNlArgs)
+ILQR_INTERNAL bool sensor_registered(const char* name);
+ILQR_INTERNAL long long sensor_abi_word();
 
 // ---- defined in ilqr_model_compile.cpp
 // what the structure probe found of a large model's callables

@@ -14,7 +14,8 @@
 module IterativeLQRAMD
 
 export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO, estimate_predict!, estimate_update!, mpc_run_est!, Estimator, estimate_update_linear!, plant_measure_linear!, mpc_run_sensor!, Sensor,
-       set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace
+       set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace,
+       compile_sensor, load_sensor_library, sensor_dims, sensor_linearise!, plant_measure_sensor!, estimate_update_sensor!, mpc_run_nlsensor!
 
 import Libdl
 
@@ -908,6 +909,152 @@ function trace(s::Solver, capacity::Integer)
     out = Array{Float64,3}(undef, 8, capacity, s.B)
     check(ccall((:ilqr_get_trace, LIB[]), Cint, (Ptr{Cvoid}, Ptr{Float64}), s.handle, out))
     return out
+end
+
+# ---- a nonlinear sensor y = h(x, s) + v compiled as a module of its own (ilqr_compile_sensor). `source` defines
+# `ILQR_SENSOR_FN void sensor_row(int j, double* y, double* dydx, const double* x, const double* s)` (include/ilqr_hip.h): what
+# Symbolics.build_function(..., target = CTarget()) emits per row of h and of its Jacobian, one case of a switch each.
+# ilqr_sensor_source, field for field
+struct SensorSource
+    name::Cstring
+    nx::Int32
+    ny::Int32
+    ns::Int32
+    source::Cstring
+    flags::Int32
+end
+
+# Returns (registered name, module path). (The symbol is looked up by hand, as mpc_run_io!'s: the struct goes by reference.)
+function compile_sensor(name::String, nx::Integer, ny::Integer, ns::Integer, source::String)
+    reg = zeros(UInt8, 256); path = zeros(UInt8, 4096)
+    GC.@preserve name source begin
+        src = SensorSource(Base.unsafe_convert(Cstring, name), Int32(nx), Int32(ny), Int32(ns), Base.unsafe_convert(Cstring, source), Int32(0))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_compile_sensor)
+        check(ccall(fn, Cint, (Ref{SensorSource}, Ptr{UInt8}, Csize_t, Ptr{UInt8}, Csize_t), src, reg, length(reg), path, length(path)))
+    end
+    return unsafe_string(pointer(reg)), unsafe_string(pointer(path))
+end
+load_sensor_library(path::String) = check(ccall((:ilqr_load_sensor_library, LIB[]), Cint, (Cstring,), path))
+register_sensor(vtable::Ptr{Cvoid}) = check(ccall((:ilqr_register_sensor, LIB[]), Cint, (Ptr{Cvoid},), vtable))
+sensor_count() = Int(ccall((:ilqr_sensor_count, LIB[]), Cint, ()))
+sensor_name(i::Integer) = unsafe_string(ccall((:ilqr_sensor_name, LIB[]), Cstring, (Int32,), i))
+function sensor_dims(sensor::String)
+    nx = Ref{Int32}(0); ny = Ref{Int32}(0); ns = Ref{Int32}(0)
+    check(ccall((:ilqr_sensor_dims, LIB[]), Cint, (Cstring, Ref{Int32}, Ref{Int32}, Ref{Int32}), sensor, nx, ny, ns))
+    return Int(nx[]), Int(ny[]), Int(ns[])
+end
+
+# s :: ns shared by the batch or (ns, B) one column per instance; nothing where the sensor has no parameters
+sensor_s(s) = s === nothing ? Ptr{Float64}(C_NULL) : pointer(s)
+per_instance_s(s) = Int32(s !== nothing && ndims(s) == 2 ? 1 : 0)
+
+# The sensor linearised at x_lin :: (nx, B) (ilqr_sensor_linearise). Returns (H :: (nx, ny, B), column-major here is the header's
+# [B][ny][nx]; yhat :: (ny, B)); with x_prior the reference output of an iterated filter.
+function sensor_linearise!(s::Solver, sensor::String, x_lin::Matrix{Float64}; sp = nothing, x_prior::Union{Nothing,Matrix{Float64}} = nothing)
+    _, ny, _ = sensor_dims(sensor)
+    H = Array{Float64,3}(undef, s.nx, ny, s.B); yhat = Matrix{Float64}(undef, ny, s.B)
+    GC.@preserve sp begin
+        check(ccall((:ilqr_sensor_linearise, LIB[]), Cint,
+                    (Ptr{Cvoid}, Cstring, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, sensor, per_instance_s(sp), sensor_s(sp), x_lin, x_prior === nothing ? Ptr{Float64}(C_NULL) : x_prior, H, yhat))
+    end
+    return H, yhat
+end
+
+# What the sensor reads of the plant states x :: (nx, B) (ilqr_plant_measure_sensor). Returns y :: (ny, B).
+function plant_measure_sensor!(s::Solver, sensor::String, x::Matrix{Float64}; sp = nothing, step::Integer = 0,
+                               sigma_y::Union{Nothing,Vector{Float64}} = nothing, seed::Integer = 0, first_instance::Integer = 0)
+    _, ny, _ = sensor_dims(sensor)
+    y = Matrix{Float64}(undef, ny, s.B)
+    GC.@preserve sp begin
+        check(ccall((:ilqr_plant_measure_sensor, LIB[]), Cint,
+                    (Ptr{Cvoid}, Cstring, Int32, Ptr{Float64}, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, sensor, per_instance_s(sp), sensor_s(sp), UInt64(seed), Int64(first_instance), Int32(step),
+                    sigma_y === nothing ? Ptr{Float64}(C_NULL) : sigma_y, x, y))
+    end
+    return y
+end
+
+# The measurement update of the (iterated) extended Kalman filter with the sensor (ilqr_estimate_update_sensor); xhat and P are
+# updated in place. Returns (innovation :: (ny, B), nis :: B, first_bad :: B).
+function estimate_update_sensor!(s::Solver, sensor::String, xhat::Matrix{Float64}, P::Array{Float64,3}, y::Matrix{Float64}, r::Vector{Float64};
+                                 sp = nothing, iterations::Integer = 1)
+    _, ny, _ = sensor_dims(sensor)
+    @assert size(xhat) == (s.nx, s.B) && size(P) == (s.nx, s.nx, s.B) && size(y) == (ny, s.B) && length(r) == ny
+    innovation = Matrix{Float64}(undef, ny, s.B)
+    nis = Vector{Float64}(undef, s.B)
+    first_bad = Vector{Int32}(undef, s.B)
+    GC.@preserve sp begin
+        check(ccall((:ilqr_estimate_update_sensor, LIB[]), Cint,
+                    (Ptr{Cvoid}, Cstring, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Int32}),
+                    s.handle, sensor, per_instance_s(sp), sensor_s(sp), Int32(iterations), r, y, xhat, P, innovation, nis, first_bad))
+    end
+    return innovation, nis, first_bad
+end
+
+# The device forms take raw device pointers on the handle's device (ilqr_*_device); r and sigma_y stay host vectors.
+sensor_linearise_device!(s::Solver, sensor::String, per::Integer, d_s::Ptr{Float64}, d_x_lin::Ptr{Float64}, d_x_prior::Ptr{Float64}, d_H::Ptr{Float64},
+                         d_yhat::Ptr{Float64}) =
+    check(ccall((:ilqr_sensor_linearise_device, LIB[]), Cint,
+                (Ptr{Cvoid}, Cstring, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), s.handle, sensor, Int32(per), d_s,
+                d_x_lin, d_x_prior, d_H, d_yhat))
+plant_measure_sensor_device!(s::Solver, sensor::String, per::Integer, d_s::Ptr{Float64}, seed::Integer, first_instance::Integer, step::Integer,
+                             sigma_y::Ptr{Float64}, d_x::Ptr{Float64}, d_y::Ptr{Float64}) =
+    check(ccall((:ilqr_plant_measure_sensor_device, LIB[]), Cint,
+                (Ptr{Cvoid}, Cstring, Int32, Ptr{Float64}, UInt64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), s.handle, sensor, Int32(per),
+                d_s, UInt64(seed), Int64(first_instance), Int32(step), sigma_y, d_x, d_y))
+estimate_update_sensor_device!(s::Solver, sensor::String, per::Integer, d_s::Ptr{Float64}, iterations::Integer, r::Vector{Float64}, d_y::Ptr{Float64},
+                               d_xhat::Ptr{Float64}, d_P::Ptr{Float64}, d_innovation::Ptr{Float64}, d_nis::Ptr{Float64}, d_first_bad::Ptr{Int32}) =
+    check(ccall((:ilqr_estimate_update_sensor_device, LIB[]), Cint,
+                (Ptr{Cvoid}, Cstring, Int32, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}), s.handle, sensor, Int32(per), d_s, Int32(iterations), r, d_y, d_xhat, d_P, d_innovation, d_nis, d_first_bad))
+
+# ilqr_nl_sensor, field for field
+struct NlSensor
+    sensor::Cstring
+    ns_per_instance::Int32
+    s::Ptr{Float64}
+    r::Ptr{Float64}
+    q::Ptr{Float64}
+    sigma_y::Ptr{Float64}
+    iterations::Int32
+end
+
+# mpc_run_sensor! with the compiled nonlinear sensor (ilqr_mpc_run_nlsensor): r and sigma_y :: ny, sp :: ns or (ns, B). Returns
+# (x, u, log, first_nonfinite, y_cl :: (ny, periods, B), saturated, xhat, pdiag, nis, P0). (The symbol is looked up by hand, as
+# mpc_run_io!'s.)
+function mpc_run_nlsensor!(s::Solver, sensor::String, r::Vector{Float64}, P0::Array{Float64,3}; sp = nothing, iterations::Integer = 1,
+                           periods::Integer, steps::Integer = 1, plant_feedback::Bool = false, shift_feedback::Bool = false,
+                           shift_tail::Symbol = :hold, warm::Bool = true, duals_tail::Symbol = :hold, duals_penalty::Symbol = :keep,
+                           seed::Integer = 0, first_instance::Integer = 0, sigma_x::Union{Nothing,Vector{Float64}} = nothing,
+                           x0::Union{Nothing,Matrix{Float64}} = nothing, xhat0::Union{Nothing,Matrix{Float64}} = nothing,
+                           q::Union{Nothing,Vector{Float64}} = nothing, sigma_y::Union{Nothing,Vector{Float64}} = nothing,
+                           u_min::Union{Nothing,Vector{Float64}} = nothing, u_max::Union{Nothing,Vector{Float64}} = nothing, delay::Integer = 0)
+    _, ny, _ = sensor_dims(sensor)
+    @assert length(r) == ny && size(P0) == (s.nx, s.nx, s.B)
+    R = periods * steps
+    x = Array{Float64,3}(undef, s.nx, R + 1, s.B); u = Array{Float64,3}(undef, s.nu, R, s.B)
+    log = Array{Float64,3}(undef, 9, periods, s.B); nf = Vector{Int32}(undef, s.B)
+    y_cl = Array{Float64,3}(undef, ny, periods, s.B); saturated = Vector{Int32}(undef, s.B)
+    xhat = Array{Float64,3}(undef, s.nx, periods, s.B); pdiag = Array{Float64,3}(undef, s.nx, periods, s.B); nis = Matrix{Float64}(undef, periods, s.B)
+    nul = Ptr{Float64}(C_NULL)
+    ptr(v) = v === nothing ? nul : pointer(v)
+    check(ccall((:ilqr_set_options, LIB[]), Cint, (Ptr{Cvoid}, Ref{Options}), s.handle, s.options))
+    GC.@preserve sensor sp r q sigma_y sigma_x u_min u_max begin
+        d = MpcDesc(Int32(periods), Int32(steps), Int32(plant_feedback ? 1 : 0), Int32(shift_feedback ? 1 : 0),
+                    Int32(shift_tail === :hold ? 0 : 1), Int32(warm ? 1 : 0), Int32(duals_tail === :hold ? 0 : 1),
+                    Int32(duals_penalty === :keep ? 0 : 1), UInt64(seed), Int64(first_instance), ptr(sigma_x))
+        io = PlantIO(ptr(u_min), ptr(u_max), nul, Int32(delay), Int32(0))
+        sens = NlSensor(Base.unsafe_convert(Cstring, sensor), per_instance_s(sp), sensor_s(sp), pointer(r), ptr(q), ptr(sigma_y), Int32(iterations))
+        fn = Libdl.dlsym(Libdl.dlopen(LIB[]), :ilqr_mpc_run_nlsensor)
+        check(ccall(fn, Cint, (Ptr{Cvoid}, Ref{MpcDesc}, Ref{PlantIO}, Ref{NlSensor}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                               Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, d, io, sens, x0 === nothing ? nul : x0, xhat0 === nothing ? nul : xhat0, P0, nul, nul, x, u, log, nf, nul, nul, y_cl,
+                    saturated, xhat, pdiag, nis))
+    end
+    return x, u, log, nf, y_cl, saturated, xhat, pdiag, nis, P0
 end
 
 end # module

@@ -1,4 +1,4 @@
-"""Compile the C-source model modules the examples and the GPU tests use (ilqr_compile_model: hipcc as a child process, no GPU
+"""Compile the C-source model modules and the sensor modules the examples and the GPU tests use (ilqr_compile_model, ilqr_compile_sensor: hipcc as a child process, no GPU
 needed) into iterativelqr.jl_amd/lib/models/, the library's module cache — so that a GPU box that receives the tree finds them
 built (the dense 64 x 16 module alone takes a minute). Called by __graft_entry__.build()."""
 import ctypes as C
@@ -81,6 +81,24 @@ def main(verbose=True):
             for reg, path in pool.map(lambda job: pkg.api.compile_model(*job), lowered):
                 if verbose:
                     print("model module %s (symbolic): %s" % (reg, os.path.basename(path)))
+        # sensor modules (ilqr_compile_sensor): the example's hand-written one, and the sensors of tests/sensor_nl_ref.py through the
+        # symbolic generator. The family is the tests' own: a tree without that file builds everything else
+        import re
+        literal = ex("mpc_range.c").decode().split("/* SENSOR SOURCE BEGIN */")[1].split("/* SENSOR SOURCE END */")[0]
+        text = "".join(line.replace("\\n", "\n") for line in re.findall(r'"(.*)"', literal))            # the C string, line by line
+        reg, path = pkg.compile_sensor_source("range2", 3, 2, 4, text)
+        if verbose:
+            print("sensor module %s (C source): %s" % (reg, os.path.basename(path)))
+        if os.path.exists(os.path.join(ROOT, "tests", "sensor_nl_ref.py")):
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import sensor_nl_ref as NL
+            for key in NL.SENSORS:                 # (one after the other: a few seconds each, and the registry is not written from two threads)
+                reg = NL.compiled(pkg, key)
+                if verbose:
+                    print("sensor module %s (symbolic)" % reg)
+            reg = NL.compiled_readback(pkg)
+            if verbose:
+                print("sensor module %s (C source)" % reg)
     finally:
         if old is None:
             os.environ.pop("ILQR_NO_STRUCTURE_PROBE", None)
