@@ -8,6 +8,7 @@ Julia closure, a C++ struct of `__device__` functions is emitted that the
 solve kernels (csrc/ilqr_device.hpp) are instantiated with.
 """
 import hashlib
+import re
 import threading
 
 import sympy as sp
@@ -965,7 +966,10 @@ def generate_sensor_source(name, h, nx, ns):
     """The C source ilqr_compile_sensor takes, from a user function h(x, s) on symbols (x: nx states, s: ns sensor parameters, returns
     the ny outputs): `ILQR_SENSOR_FN void sensor_row(int j, double* y, double* dydx, const double* x, const double* s)` as a
     `switch (j)` with one case per row, each with its own common subexpressions, writing *y = h_j and only the structurally non-zero
-    partials dydx[k] = ∂h_j/∂x_k (dydx arrives zeroed). Returns (ny, source). `name` only labels the source."""
+    partials dydx[k] = ∂h_j/∂x_k (dydx arrives zeroed). Returns (ny, source). `name` only labels the source.
+    h may use what C's math.h has (sin .. atanh, atan2, exp, log, sqrt, cbrt, pow, Abs, sign, Min, Max, floor, ceiling, erf, gamma ..),
+    Piecewise and relations; a function the printer has no C for, in h or in a derivative (sign's is a DiracDelta), is refused here
+    with a ValueError that names it, not left for the compiler to find."""
     pr = _SensorPrinter({"strict": False})
     x, s, rows, jac = sensor_expressions(h, nx, ns)
     ny = len(rows)
@@ -984,4 +988,8 @@ def generate_sensor_source(name, h, nx, ns):
         out += ["            dydx[%d] = %s;" % (k, pr.doprint(e.xreplace(sub))) for k, e in enumerate(red[1:]) if e != 0]
         out.append("        } break;")
     out += ["        default: break;", "    }", "}", ""]
-    return ny, "\n".join(out)
+    text = "\n".join(out)
+    unsupported = sorted(set(re.findall(r"/\* Not supported in C: \*/\s*/\* (\w+) \*/", text)))      # a non-strict printer marks what it cannot express
+    if unsupported:
+        raise ValueError("sensor %s: h or its Jacobian contains %s, which C cannot express" % (name, ", ".join(unsupported)))
+    return ny, text

@@ -71,17 +71,39 @@ SENSORS = {
     "mix32": ("synth32", 32, 33, 1, _mix32),
 }
 BY_MODEL = {"car_obs": ("range_heading", "beacons2"), "acrobot": ("encoder",), "synth12": ("mix12", "wide12"), "synth32": ("mix32",)}
+# Further tables of the same rows (tests/sensor_nl_sizes.py) are looked up by the same functions once registered. A row may carry a
+# sixth field, a dict: "sym", what h is traced over in place of the sympy module; "h" and "jacobian", (x, s) -> fp64 arrays from
+# another high-precision method, in place of the numpy evaluation and the complex step (a real x only).
+_TABLES = [SENSORS]
+
+
+def register(table):
+    assert all(k not in t for t in _TABLES for k in table if t is not table)
+    if not any(t is table for t in _TABLES):
+        _TABLES.append(table)
+
+
+def entry(key):
+    for t in _TABLES:
+        if key in t:
+            return t[key]
+    raise KeyError(key)
+
+
+def _other(key):
+    e = entry(key)
+    return e[5] if len(e) > 5 else {}
 
 
 def dims(key):
-    return SENSORS[key][1:4]
+    return entry(key)[1:4]
 
 
 def symbolic(key):
     """h(x, s) on sympy symbols, as codegen.generate_sensor_source / api.compile_sensor take it"""
     import sympy as sp
-    f = SENSORS[key][4]
-    return lambda x, s: f(x, s, sp)
+    f, m = entry(key)[4], _other(key).get("sym", sp)
+    return lambda x, s: f(x, s, m)
 
 
 _COMPILED = {}
@@ -90,7 +112,7 @@ _COMPILED = {}
 def compiled(pkg, key):
     """the registered name of the sensor's module, compiled (or found in the module cache) once per process"""
     if key not in _COMPILED:
-        _, nx, _, ns, _ = SENSORS[key]
+        nx, _, ns = dims(key)
         _COMPILED[key] = pkg.compile_sensor("nl_" + key, symbolic(key), nx, ns)[0]
     return _COMPILED[key]
 
@@ -119,7 +141,7 @@ def compiled_readback(pkg):
 
 def s_shared(key):
     """[ns]: beacon positions away from the car's paths; gains of order one"""
-    ns = SENSORS[key][3]
+    ns = dims(key)[2]
     return {"beacons2": np.array([3.0, 2.0, -2.0, 3.0])}.get(key, 0.5 + 0.25 * np.cos(1.0 + np.arange(ns)))
 
 
@@ -140,7 +162,7 @@ def sigma_y(ny):
 def readings(key, states, s):
     """y [B, ny] = h(the states E.start gives as its measurement) + a fixed pattern; s [ns] or [B, ns]"""
     B = states.shape[0]
-    ny = SENSORS[key][2]
+    ny = dims(key)[1]
     y = np.stack([h(key, states[b], s if np.ndim(s) == 1 else s[b]) for b in range(B)])
     return y + 0.01 * np.sin(0.3 + np.arange(B)[:, None] + 2.0 * np.arange(ny)[None, :])
 
@@ -148,14 +170,18 @@ def readings(key, states, s):
 # ------------------------------------------------------------------------------------------------------------- the operation
 def h(key, x, s):
     """y [ny] of one instance (real or complex x)"""
+    if "h" in _other(key):
+        return _other(key)["h"](np.asarray(x, dtype=np.float64), np.asarray(s, dtype=np.float64))
     with np.errstate(all="ignore"):
-        return np.array(SENSORS[key][4](np.asarray(x), np.asarray(s, dtype=np.float64), np), dtype=np.asarray(x).dtype)
+        return np.array(entry(key)[4](np.asarray(x), np.asarray(s, dtype=np.float64), np), dtype=np.asarray(x).dtype)
 
 
 def jacobian(key, x, s):
     """H [ny, nx] by the complex step"""
+    if "jacobian" in _other(key):
+        return _other(key)["jacobian"](np.asarray(x, dtype=np.float64), np.asarray(s, dtype=np.float64))
     n = len(x)
-    H = np.zeros((SENSORS[key][2], n))
+    H = np.zeros((dims(key)[1], n))
     for k in range(n):
         z = np.array(x, dtype=np.complex128)
         z[k] += 1j * STEP

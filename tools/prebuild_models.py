@@ -99,6 +99,14 @@ def main(verbose=True):
             reg = NL.compiled_readback(pkg)
             if verbose:
                 print("sensor module %s (C source)" % reg)
+            # the size sweep's and the function family's sensors (tests/sensor_nl_sizes.py) the same way; a dense switch of 64 cases
+            # among them
+            if os.path.exists(os.path.join(ROOT, "tests", "sensor_nl_sizes.py")):
+                import sensor_nl_sizes as NZ
+                for key in NZ.KEYS:
+                    reg = NL.compiled(pkg, key)
+                    if verbose:
+                        print("sensor module %s (symbolic)" % reg)
     finally:
         if old is None:
             os.environ.pop("ILQR_NO_STRUCTURE_PROBE", None)

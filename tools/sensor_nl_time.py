@@ -72,6 +72,12 @@ def resources(pkg):
             ny, src = pkg.codegen.generate_sensor_source(key, NL.symbolic(key), nx, ns)
             jobs.append(("nl_" + key, nx, ny, ns, src))
         jobs.append(("nl_readback", 4, 2, 0, NL.READBACK_SOURCE))
+        if os.path.exists(os.path.join(root, "tests", "sensor_nl_sizes.py")):
+            import sensor_nl_sizes as NZ
+            for key in NZ.KEYS:
+                nx, _, ns = NL.dims(key)
+                ny, src = pkg.codegen.generate_sensor_source(key, NL.symbolic(key), nx, ns)
+                jobs.append(("nl_" + key, nx, ny, ns, src))
     fields = ("VGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]")
     with tempfile.TemporaryDirectory() as tmp:
         for key, nx, ny, ns, src in jobs:
