@@ -489,6 +489,40 @@ int ilqr_estimate_update(ilqr_handle* h,
 int ilqr_estimate_update_device(ilqr_handle* h, const int32_t* measured, const double* r, const double* d_y, double* d_xhat, double* d_P,
                                 double* d_innovation, double* d_nis, int32_t* d_first_bad);
 
+/* A state covariance propagated down the handle's plan under its feedback policy: how far the closed-loop state and the actions are
+ * expected to stray from the plan at each step of the horizon, to first order, when the plan starts from an estimate with covariance
+ * P0 (the filter's P) and the model is disturbed by process noise of variances q. S = steps, 1 <= S <= T − 1; feedback 0 or 1;
+ * P0 [B][nx][nx] row-major: only the elements with row >= column are read, and they are mirrored. For t = 0 .. S−1, with Σ_0 = P0:
+ *     A   = ∂f/∂x, Bm = ∂f/∂u at (x̄_t, ū_t, θ_t) as the handle holds them — the NOMINAL point of the plan, not an estimate — the
+ *           model's own dynamics Jacobians, the ones the solver linearises with; the selector columns of a lowered problem are θ_t's
+ *     Φ   = A + Bm · K_t where feedback, else Φ = A. With feedback == 0, K is not read: a NaN in K changes nothing
+ *     udiag[b][t][r] = Σ_a Σ_b K_t(r, a) Σ_t(a, b) K_t(r, b) where feedback, else 0: the variance of action r
+ *     Σ_{t+1} = Φ Σ_t Φᵀ + diag(q): the elements with row >= column are computed and each is copied to its mirror, so the stored
+ *           matrix is exactly symmetric
+ * Outputs, every one may be NULL, but not all of them together: sdiag [B][S+1][nx] the diagonals of Σ_0 .. Σ_S; udiag [B][S][nu];
+ * sigma [B][S+1][nx][nx] every Σ_t; P_out [B][nx][nx] = Σ_S, which may alias P0; first_nonfinite [B]: −1, or the first t in 0 .. S
+ * with a non-finite entry on the diagonal of Σ_t — that instance's later outputs are unspecified, other instances are unaffected.
+ * The summation orders are the kernel's; they are fixed by the model's sizes alone, so an instance's bits depend neither on B nor on
+ * its neighbours, nor on which optional outputs are asked for.
+ * The call READS the handle: workspace, scalars, statistics, trace and timing are unchanged. Refused (ILQR_ERR_INVALID) before any
+ * launch: steps out of range; feedback other than 0 or 1; a null P0; all outputs null; a negative or non-finite q entry; nx > 64 or
+ * nu > 16; feedback == 1 on a handle that holds no policy yet (ilqr_rollout_policy's rule). Host form: synchronous, works on a
+ * sharded handle (each instance goes to the device that owns it). Device form: every array a device pointer, asynchronous on the
+ * handle's stream, refused on a sharded handle.
+ * Not offered: actuator limits (a saturated action has no gain); a non-diagonal Q; measurement updates along the horizon;
+ * constraint-row variances and automatic back-offs; integration into ilqr_mpc_run_* — the device form on the handle's stream is what
+ * a caller enqueues between their own per-period calls. */
+int ilqr_plan_covariance(ilqr_handle* h, int32_t steps, int32_t feedback,
+                         const double* q,                 /* HOST, NULL (= 0) or [nx], finite, >= 0 */
+                         const double* P0,                /* [B][nx][nx] */
+                         double* sdiag,                   /* NULL, or [B][S+1][nx] */
+                         double* udiag,                   /* NULL, or [B][S][nu] */
+                         double* sigma,                   /* NULL, or [B][S+1][nx][nx] */
+                         double* P_out,                   /* NULL, or [B][nx][nx]; may alias P0 */
+                         int32_t* first_nonfinite);       /* NULL, or [B] */
+int ilqr_plan_covariance_device(ilqr_handle* h, int32_t steps, int32_t feedback, const double* q, const double* d_P0, double* d_sdiag,
+                                double* d_udiag, double* d_sigma, double* d_P_out, int32_t* d_first_nonfinite);
+
 /* ilqr_mpc_run_io with the filter between sensor and controller. Per period p, with k = steps:
  *   delay == 0:  1. the plant step on xp;  2. y = ilqr_plant_measure_device(step = (p+1)·k, sigma_y, xp);
  *                3. ilqr_estimate_predict_device(k, plant_feedback, the limits, q) under the plan in flight;
@@ -1033,6 +1067,9 @@ int ilqr_device_math(const char* fn, const double* x, double* y, int32_t n);
 /* Model registry (generated model modules call this from a static initialiser). */
 struct ilqr_model_vtable;
 int ilqr_register_model(const struct ilqr_model_vtable* vt);
+/* The kernels a model module registers beside its vtable, under the same name and after it (ext: a const ilqr_model_ext*,
+ * csrc/ilqr_device.hpp); a table built against other headers, or for a model that is not registered, is refused. */
+int ilqr_register_model_ext(const void* ext);
 int ilqr_model_count(void);
 const char* ilqr_model_name(int32_t i);
 /* Large models (nx > 4 or nu > 4): how many Jacobian entries per timestep the kernels treat as state-dependent and how many

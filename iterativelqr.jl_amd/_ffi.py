@@ -211,6 +211,8 @@ SYMBOLS = {
     "ilqr_estimate_update": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p,
                                        C.POINTER(C.c_int32)]),
     "ilqr_estimate_update_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), c_double_p] + [C.c_void_p] * 6),
+    "ilqr_plan_covariance": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [c_double_p] * 6 + [C.POINTER(C.c_int32)]),
+    "ilqr_plan_covariance_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_double_p] + [C.c_void_p] * 6),
     "ilqr_mpc_run_est": (C.c_int, [C.c_void_p, C.POINTER(MpcDesc), C.POINTER(PlantIO), C.POINTER(Estimator), c_double_p, c_double_p, c_double_p,
                                    c_double_p, c_double_p, c_double_p, c_double_p, c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p,
                                    c_double_p, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
@@ -278,6 +280,7 @@ SYMBOLS = {
     "ilqr_synthetic_inputs": (C.c_int, [C.c_char_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, c_double_p, c_double_p]),
     "ilqr_device_math": (C.c_int, [C.c_char_p, c_double_p, c_double_p, C.c_int32]),
     "ilqr_register_model": (C.c_int, [C.c_void_p]),
+    "ilqr_register_model_ext": (C.c_int, [C.c_void_p]),
     "ilqr_model_count": (C.c_int, []),
     "ilqr_model_name": (C.c_char_p, [C.c_int32]),
     "ilqr_model_compact_sizes": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

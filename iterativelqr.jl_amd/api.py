@@ -686,6 +686,36 @@ class Solver:
         _ffi.check(_ffi.lib().ilqr_estimate_update_device(self._h, _i32p(measured), _p(r), _vp(d_y_ptr), _vp(d_xhat_ptr), _vp(d_P_ptr),
                                                           _vp(d_innovation_ptr), _vp(d_nis_ptr), _vp(d_first_bad_ptr)))
 
+    def plan_covariance_(self, P0, steps=None, feedback=True, q=None, full=False):
+        """A state covariance propagated down the handle's plan under its feedback policy (ilqr_plan_covariance): Σ_0 = P0 [B, nx, nx]
+        (the lower triangle is read and mirrored), Σ_{t+1} = Φ Σ_t Φᵀ + diag(q) for t = 0 .. steps − 1 with Φ = A + Bm K_t (feedback) or
+        A, the model's dynamics Jacobians at the nominal point (x̄_t, ū_t, θ_t). steps=None: T − 1. q [nx] (or a scalar, None = 0).
+        Reads the handle; changes none of its state. Returns a dict with sdiag [B, steps + 1, nx] (the diagonals of Σ_0 .. Σ_steps),
+        udiag [B, steps, nu] (the variances of the actions, 0 without feedback), P [B, nx, nx] (= Σ_steps), first_nonfinite [B] (−1,
+        or the first t with a non-finite entry on the diagonal of Σ_t) and, with full, sigma [B, steps + 1, nx, nx]."""
+        S = self.T - 1 if steps is None else int(steps)
+        _, q, _ = _variances(self.nx, None, q, None)
+        P0 = np.ascontiguousarray(P0, dtype=np.float64)
+        if P0.shape != (self.B, self.nx, self.nx):
+            raise ValueError("P0 must have shape [B, nx, nx]")
+        rows = max(S, 0)
+        out = dict(sdiag=np.empty((self.B, rows + 1, self.nx)), udiag=np.empty((self.B, rows, self.nu)), P=np.empty((self.B, self.nx, self.nx)),
+                   first_nonfinite=np.empty(self.B, dtype=np.int32))
+        if full:
+            out["sigma"] = np.empty((self.B, rows + 1, self.nx, self.nx))
+        _ffi.check(_ffi.lib().ilqr_plan_covariance(self._h, S, 1 if feedback else 0, _nul(q), _p(P0), _p(out["sdiag"]), _p(out["udiag"]),
+                                                   _nul(out.get("sigma")), _p(out["P"]), _i32p(out["first_nonfinite"])))
+        return out
+
+    def plan_covariance_device_(self, d_P0_ptr, steps=None, feedback=True, q=None, d_sdiag_ptr=None, d_udiag_ptr=None, d_sigma_ptr=None,
+                                d_P_out_ptr=None, d_first_nonfinite_ptr=None):
+        """The same with raw device pointers on the handle's device (None = not wanted; d_P_out_ptr may be d_P0_ptr); q stays a host
+        array; asynchronous on the handle's stream."""
+        S = self.T - 1 if steps is None else int(steps)
+        _, q, _ = _variances(self.nx, None, q, None)
+        _ffi.check(_ffi.lib().ilqr_plan_covariance_device(self._h, S, 1 if feedback else 0, _nul(q), _vp(d_P0_ptr), _vp(d_sdiag_ptr), _vp(d_udiag_ptr),
+                                                          _vp(d_sigma_ptr), _vp(d_P_out_ptr), _vp(d_first_nonfinite_ptr)))
+
     def plant_score_(self, x, u, w_plant=None):
         """The score of plant steps on the device (ilqr_plant_score): the realised stage cost and constraint violation of the states a
         plant visited and the actions it applied, x [B, steps + 1, nx] and u [B, steps, nu] as plant_step_ returns them (the last row

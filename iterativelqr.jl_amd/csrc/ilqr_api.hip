@@ -86,6 +86,17 @@ const ilqr_sensor_vtable* find_sensor(const char* name) {
     return nullptr;
 }
 
+// the kernels model modules register beside their vtables (ilqr_register_model_ext), by the vtable's name
+std::vector<const ilqr_model_ext*>& ext_registry() {
+    static std::vector<const ilqr_model_ext*> r;
+    return r;
+}
+const ilqr_model_ext* find_ext(const char* name) {
+    for (auto* e : ext_registry())
+        if (name && !std::strcmp(e->name, name)) return e;
+    return nullptr;
+}
+
 struct BufferDesc { const char* name; int offset; int len; };
 
 }  // namespace
@@ -113,7 +124,7 @@ enum { SHIFT_X1, SHIFT_W_TAIL, SHIFT_W_STAGE, SHIFT_STAGES };
 enum { SAMP_WEIGHTS, SAMP_U_OUT, SAMP_SIGMA, SAMP_STAGES };
 enum { PLANT_X, PLANT_W, PLANT_X_OUT, PLANT_U_OUT, PLANT_NONFINITE, PLANT_LOG, PLANT_W_PREVIEW, PLANT_COST, PLANT_VIOL, PLANT_SATURATED, PLANT_XC,
        PLANT_Y, EST_P, EST_Y, EST_INNOVATION, EST_NIS, EST_FIRST_BAD, EST_XHAT_CL, EST_PDIAG_CL, EST_NIS_CL, SENS_H, SENS_R, SENS_SIGMA, SENS_YHAT, SENS_S,
-       SENS_XLIN, SENS_XPRIOR, SENS_X0, SENS_P0, PLANT_STAGES };
+       SENS_XLIN, SENS_XPRIOR, SENS_X0, SENS_P0, PCOV_SDIAG, PCOV_UDIAG, PCOV_SIGMA, PCOV_POUT, PLANT_STAGES };
 
 struct ilqr_handle {
     const ilqr_model_vtable* vt;
@@ -184,7 +195,8 @@ struct ilqr_handle {
     // measurement and nis, and the three per-period logs of the filter; ilqr_estimate_update_linear / ilqr_plant_measure_linear /
     // ilqr_mpc_run_sensor: H, r, sigma_y and ŷ; ilqr_sensor_linearise / ilqr_plant_measure_sensor / ilqr_estimate_update_sensor /
     // ilqr_mpc_run_nlsensor: the sensor parameters s, the point of linearisation and the prior of its host form, the Jacobians H
-    // [B][ny][nx] and ŷ the update reads (in the stages of H and ŷ), and the prior (x̂₀, P₀) of the iterated filter
+    // [B][ny][nx] and ŷ the update reads (in the stages of H and ŷ), and the prior (x̂₀, P₀) of the iterated filter;
+    // ilqr_plan_covariance: P0 in the stage of the covariance, first_nonfinite in its own, sdiag, udiag, sigma and P_out
     Stage plant[PLANT_STAGES];
 };
 
@@ -586,6 +598,19 @@ int ilqr_register_model(const ilqr_model_vtable* vt) {
     for (auto& e : r)
         if (!std::strcmp(e->name, vt->name)) { e = vt; return ILQR_OK; }
     r.push_back(vt);
+    return ILQR_OK;
+}
+int ilqr_register_model_ext(const void* ext) {
+    const ilqr_model_ext* e = (const ilqr_model_ext*)ext;
+    if (!e) return ILQR_ERR_INVALID;
+    if (e->ext_version != ILQR_MODEL_EXT_VERSION || e->args_bytes != (int)sizeof(ilqr::PlanCovArgs))
+        return fail(ILQR_ERR_MODEL, "model module was built against a different library version (ABI mismatch): rebuild it");
+    if (!e->name) return ILQR_ERR_INVALID;
+    if (!find_model(e->name)) return fail(ILQR_ERR_MODEL, std::string("ilqr_register_model_ext: no model '") + e->name + "' is registered");
+    auto& r = ext_registry();
+    for (auto& x : r)
+        if (!std::strcmp(x->name, e->name)) { x = e; return ILQR_OK; }
+    r.push_back(e);
     return ILQR_OK;
 }
 int ilqr_model_count(void) { return (int)registry().size(); }
@@ -1704,6 +1729,58 @@ int ilqr_estimate_update(ilqr_handle* h, const int32_t* measured, const double* 
                           staged_out(IN_PLANT, EST_INNOVATION, innovation, n), staged_out(IN_PLANT, EST_NIS, nis, 1), staged_out(IN_PLANT, EST_FIRST_BAD, first_bad, 1)},
                       [&](ilqr_handle* s, size_t, const Staged* a) {
                           return update_launch(s, measured, r, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].i()); });
+}
+
+// ---- a state covariance down the plan under its feedback policy (ilqr_device_plancov.hpp)
+// everything that can be refused without touching the GPU; what needs no handle comes first (of q: its first entry)
+static int plancov_check(const ilqr_handle* h, int32_t steps, int32_t feedback, const double* q, const double* P0, bool any_output, const char* who) {
+    const std::string me(who);
+    if (steps < 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
+    if (feedback != 0 && feedback != 1) return fail(ILQR_ERR_INVALID, me + ": feedback must be 0 or 1");
+    if (!P0) return fail(ILQR_ERR_INVALID, me + ": null P0");
+    if (!any_output) return fail(ILQR_ERR_INVALID, me + ": every output is null");
+    ILQR_TRY(variance_check(nullptr, q, nullptr, 1, me));
+    if (!h) return fail(ILQR_ERR_INVALID, me + ": null handle");
+    if (steps > h->L.T - 1) return fail(ILQR_ERR_INVALID, me + ": steps must lie in 1 .. T-1");
+    if (h->L.nx > ilqr::PLANT_MAX_NX) return fail(ILQR_ERR_INVALID, me + ": more than 64 state components");
+    if (h->L.nu > ilqr::PLANT_MAX_NU) return fail(ILQR_ERR_INVALID, me + ": more than 16 action components");
+    ILQR_TRY(variance_check(nullptr, q, nullptr, h->L.nx, me));
+    if (feedback && !every_shard_holds(h, &ilqr_handle::has_policy))
+        return fail(ILQR_ERR_INVALID, me + ": the handle holds no policy yet (no solve and no backward_pass stage has run since the last reset)");
+    return ILQR_OK;
+}
+
+// every pointer a device pointer on h's device (the outputs: or null)
+static int plancov_launch(ilqr_handle* h, int32_t steps, int32_t feedback, const double* q, const double* P0, double* sdiag, double* udiag,
+                          double* sigma, double* P_out, int32_t* first_nonfinite) {
+    const ilqr_model_ext* e = find_ext(h->vt->name);
+    if (!e || !e->launch_plan_covariance) return fail(ILQR_ERR_MODEL, "this model module has no plan covariance kernel");
+    ilqr::PlanCovArgs a = {};
+    a.ws = h->ws; a.L = h->L; a.B = h->B; a.steps = steps; a.feedback = feedback; a.P0 = P0; a.sdiag = sdiag; a.udiag = udiag; a.sigma = sigma;
+    a.P_out = P_out; a.nonfinite = first_nonfinite;
+    for (int j = 0; q && j < h->L.nx; ++j) a.q[j] = q[j];                      // by value: the caller's array may go away at once
+    if (e->launch_plan_covariance(&a, h->stream) != 0) return fail(ILQR_ERR_HIP, "plan covariance launch failed");
+    return ILQR_OK;
+}
+
+int ilqr_plan_covariance_device(ilqr_handle* h, int32_t steps, int32_t feedback, const double* q, const double* P0, double* sdiag, double* udiag,
+                                double* sigma, double* P_out, int32_t* first_nonfinite) {
+    ILQR_TRY(plancov_check(h, steps, feedback, q, P0, sdiag || udiag || sigma || P_out || first_nonfinite, "ilqr_plan_covariance_device"));
+    if (SHARDED(h)) return refuse_sharded("ilqr_plan_covariance");
+    HIP_TRY(hipSetDevice(h->device));
+    return plancov_launch(h, steps, feedback, q, P0, sdiag, udiag, sigma, P_out, first_nonfinite);
+}
+
+int ilqr_plan_covariance(ilqr_handle* h, int32_t steps, int32_t feedback, const double* q, const double* P0, double* sdiag, double* udiag,
+                         double* sigma, double* P_out, int32_t* first_nonfinite) {
+    ILQR_TRY(plancov_check(h, steps, feedback, q, P0, sdiag || udiag || sigma || P_out || first_nonfinite, "ilqr_plan_covariance"));
+    const size_t n = (size_t)h->L.nx, m = (size_t)h->L.nu, S = (size_t)steps;
+    // P0 and P_out have stages of their own: the kernel reads the one before it writes the other, whether or not the caller's alias
+    return run_staged(h, {staged_in(IN_PLANT, EST_P, P0, n * n), staged_out(IN_PLANT, PCOV_SDIAG, sdiag, (S + 1) * n),
+                          staged_out(IN_PLANT, PCOV_UDIAG, udiag, S * m), staged_out(IN_PLANT, PCOV_SIGMA, sigma, (S + 1) * n * n),
+                          staged_out(IN_PLANT, PCOV_POUT, P_out, n * n), staged_out(IN_PLANT, PLANT_NONFINITE, first_nonfinite, 1)},
+                      [&](ilqr_handle* s, size_t, const Staged* a) {
+                          return plancov_launch(s, steps, feedback, q, a[0].d(), a[1].d(), a[2].d(), a[3].d(), a[4].d(), a[5].i()); });
 }
 
 // ---- a linear sensor y = H x + v with ny outputs (ilqr_device_sensor.hpp)

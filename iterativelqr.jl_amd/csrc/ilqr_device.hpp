@@ -2334,6 +2334,7 @@ __global__ __launch_bounds__(64) void init_rollout_large_kernel(KArgs a) {
 #include "ilqr_device_estimate.hpp"
 #include "ilqr_device_sensor.hpp"
 #include "ilqr_device_sensor_nl.hpp"
+#include "ilqr_device_plancov.hpp"
 
 // Model module interface: what a compiled model (built-in or generated by
 // iterativelqr.jl_amd/codegen.py) registers with the library.
@@ -2385,6 +2386,17 @@ extern "C" struct ilqr_model_vtable {
     // read the workspace only (ilqr_device_estimate.hpp)
     int (*launch_estimate_predict)(const ilqr::EstArgs* a, void* stream);
     int (*launch_estimate_update)(const ilqr::EstArgs* a, void* stream);
+};
+// Kernels a model module registers BESIDE its vtable, under the vtable's name (ilqr_register_model_ext, after ilqr_register_model):
+// the vtable and ILQR_MODEL_ABI_VERSION stay what they are, and a module without this table is refused by the entry points that
+// need it (ILQR_ERR_MODEL), never served by another path.
+#define ILQR_MODEL_EXT_VERSION 1    /* bump whenever PlanCovArgs or this struct change */
+extern "C" struct ilqr_model_ext {
+    int ext_version;     // ILQR_MODEL_EXT_VERSION the module was compiled against
+    int args_bytes;      // sizeof(ilqr::PlanCovArgs) it was compiled against
+    const char* name;    // the vtable's
+    // a state covariance down the plan under its feedback policy; reads the workspace only (ilqr_device_plancov.hpp)
+    int (*launch_plan_covariance)(const ilqr::PlanCovArgs* a, void* stream);
 };
 
 namespace ilqr {
@@ -2451,12 +2463,19 @@ struct ModelModule {
                                              &launch_estimate_predict<M>, &launch_estimate_update<M>};
         return &vt;
     }
+    static const ilqr_model_ext* ext() {
+        static const ilqr_model_ext e = {ILQR_MODEL_EXT_VERSION, (int)sizeof(PlanCovArgs), M::NAME, &launch_plan_covariance<M>};
+        return &e;
+    }
 };
 }  // namespace ilqr
 
 #define ILQR_DEFINE_MODEL(MODEL)                                                              \
     namespace {                                                                               \
     struct Registrar_##MODEL {                                                                \
-        Registrar_##MODEL() { ilqr_register_model(ilqr::ModelModule<MODEL>::vtable()); }      \
+        Registrar_##MODEL() {                                                                 \
+            ilqr_register_model(ilqr::ModelModule<MODEL>::vtable());                          \
+            ilqr_register_model_ext(ilqr::ModelModule<MODEL>::ext());                         \
+        }                                                                                     \
     } registrar_##MODEL;                                                                      \
     }

@@ -13,7 +13,7 @@
 # are passed as (nx, T, B) / (nu, T-1, B) column-major views of the same memory).
 module IterativeLQRAMD
 
-export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO, estimate_predict!, estimate_update!, mpc_run_est!, Estimator, estimate_update_linear!, plant_measure_linear!, mpc_run_sensor!, Sensor,
+export Options, Solver, Dynamics, Cost, Constraint, initialize_controls!, initialize_states!, initialize_rollout!, initialize_rollout_candidates!, sample_rollout_candidates!, candidate_noise, shift_horizon!, shift_duals!, solve_warm!, plant_step!, mpc_run!, MpcDesc, plant_score!, plant_score_device!, mpc_run_preview!, plant_step_limited!, plant_measure!, mpc_run_io!, PlantIO, estimate_predict!, plan_covariance!, plan_covariance_device!, estimate_update!, mpc_run_est!, Estimator, estimate_update_linear!, plant_measure_linear!, mpc_run_sensor!, Sensor,
        set_parameters!, solve!, solve_shared_step!, get_trajectory, get_policy, rollout_policy, stats, set_kernel_variant!, set_handover!, set_handover_live!, set_handover_mark!, enable_trace!, trace,
        compile_sensor, load_sensor_library, sensor_dims, sensor_linearise!, plant_measure_sensor!, estimate_update_sensor!, mpc_run_nlsensor!
 
@@ -459,6 +459,39 @@ function estimate_predict!(s::Solver, xhat::Matrix{Float64}, P::Array{Float64,3}
                 s.handle, Int32(steps), Int32(feedback ? 1 : 0), u_min === nothing ? nul : u_min, u_max === nothing ? nul : u_max,
                 q === nothing ? nul : q, xhat, P))
     return xhat, P
+end
+
+# A state covariance propagated down the handle's plan under its feedback policy (ilqr_plan_covariance): Σ_0 = P0 :: (nx, nx, B)
+# (one triangle is read and mirrored), Σ_{t+1} = Φ Σ_t Φᵀ + diag(q) with Φ = A + Bm K_t (feedback) or A at the nominal point of the
+# plan. Reads the handle. Returns (sdiag :: (nx, steps + 1, B), udiag :: (nu, steps, B), P :: (nx, nx, B) = Σ_steps,
+# first_nonfinite :: B, sigma :: (nx, nx, steps + 1, B) or nothing).
+function plan_covariance!(s::Solver, P0::Array{Float64,3}; steps::Integer = s.T - 1, feedback::Bool = true,
+                          q::Union{Nothing,Vector{Float64}} = nothing, full::Bool = false)
+    @assert size(P0) == (s.nx, s.nx, s.B) && 1 <= steps <= s.T - 1 && (q === nothing || length(q) == s.nx)
+    nul = Ptr{Float64}(C_NULL)
+    sdiag = Array{Float64,3}(undef, s.nx, steps + 1, s.B)
+    udiag = Array{Float64,3}(undef, s.nu, steps, s.B)
+    sigma = full ? Array{Float64,4}(undef, s.nx, s.nx, steps + 1, s.B) : nothing
+    P = Array{Float64,3}(undef, s.nx, s.nx, s.B)
+    nf = Vector{Int32}(undef, s.B)
+    check(ccall((:ilqr_plan_covariance, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                s.handle, Int32(steps), Int32(feedback ? 1 : 0), q === nothing ? nul : q, P0, sdiag, udiag, full ? sigma : nul, P, nf))
+    return sdiag, udiag, P, nf, sigma
+end
+
+# The same on device arrays of the handle's device (C_NULL: not wanted; d_P_out may be d_P0), asynchronous on the handle's stream;
+# q stays a host vector.
+function plan_covariance_device!(s::Solver, d_P0::Ptr{Float64}; steps::Integer = s.T - 1, feedback::Bool = true,
+                                 q::Union{Nothing,Vector{Float64}} = nothing, d_sdiag::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                                 d_udiag::Ptr{Float64} = Ptr{Float64}(C_NULL), d_sigma::Ptr{Float64} = Ptr{Float64}(C_NULL),
+                                 d_P_out::Ptr{Float64} = Ptr{Float64}(C_NULL), d_first_nonfinite::Ptr{Int32} = Ptr{Int32}(C_NULL))
+    @assert 1 <= steps <= s.T - 1 && (q === nothing || length(q) == s.nx)
+    check(ccall((:ilqr_plan_covariance_device, LIB[]), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
+                s.handle, Int32(steps), Int32(feedback ? 1 : 0), q === nothing ? Ptr{Float64}(C_NULL) : q, d_P0, d_sdiag, d_udiag, d_sigma,
+                d_P_out, d_first_nonfinite))
+    return nothing
 end
 
 # The measurement update (ilqr_estimate_update): the components j of y :: (nx, B) with measured[j] == 1 (nothing: all) are taken in
